@@ -8,6 +8,12 @@ with scalars and bases already resident in HBM, plus the exchange step: an
 all-gather of the per-rank partial points over RCCL and their fold on the host
 (EC addition is not limb-wise, so no all-reduce).  `value` = N*2^20 / step time.
 
+A plain run is that headline alone: inputs and resident bases set up, warmup,
+K timed steps, the line.  `--dump-outputs DIR` then writes the last timed
+step's result (DIR/msm_result.npy; the inputs are seeded, so two builds can be
+compared output for output).  Everything below the headline's `roofline` --
+every other leg, the kernel breakdowns, the CPU baselines -- runs with `--full`.
+
 `roofline` is for the dominant kernel (k_accumulate), its duration measured
 live with HIP events on the context stream over the timed region.  The
 headline runs against the resident SRS bases (their row table, like
@@ -79,10 +85,32 @@ def parse(argv=None):
                     help="also time BASELINE config 3: 16 simple-example proofs at k = 14 per GPU (1) or skip (0)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous check only: no GPU work (gloo), prints the JSON skeleton")
-    ap.add_argument("--detail", default=DETAIL_DEFAULT,
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg (kernel breakdowns, variable-base, host-scalar, "
+                         "drop-in and small-n legs, CPU baselines, 2^22 / strong / fixed-base MSMs, NTTs, accumulator "
+                         "and instance-commitment legs); the options above select among them.  Without it the run "
+                         "is the headline alone: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--detail", default=None,
                     help="file for the full per-leg record (kernel breakdowns, small_n curve, configs); "
-                         "the stdout line carries only compact leg summaries ('' = do not write it)")
-    return ap.parse_args(argv)
+                         "the stdout line carries only compact leg summaries (default: with --full "
+                         f"{DETAIL_DEFAULT}, else none; '' = do not write it)")
+    args = ap.parse_args(argv)
+    if args.detail is None:
+        args.detail = DETAIL_DEFAULT if args.full else ""
+    if not args.full:
+        headline_only(args)
+    return args
+
+
+def headline_only(args):
+    """A plain run: switch every leg but the headline off (the headline's own
+    sub-legs are keyed on args.full in main / run_msm_leg)."""
+    args.no_cpu = True
+    for k in ("fixed", "fixed23", "logn22", "strong_logn", "small_n", "ntt_logn", "ntt_large_logn", "accum_batch",
+              "accum_b16", "accum_b32", "accum_large", "inst_batch"):
+        setattr(args, k, 0)
 
 
 # ---------------------------------------------------------------------------
@@ -381,9 +409,11 @@ def main():
         ctx.set_window(args.window)
     dev = torch.device("cuda", local)
     i0, _ = shard_range(rank, world, n)
-    leg = run_msm_leg(args, ctx, dist, dev, world, curve, n, i0, roofline=True, breakdown=True,
-                      host_leg=(world == 1))
+    leg = run_msm_leg(args, ctx, dist, dev, world, curve, n, i0, roofline=True, breakdown=args.full,
+                      host_leg=(args.full and world == 1))
     d_s, d_b, result = leg.pop("_d_s"), leg.pop("_d_b"), leg.pop("_result")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
     gathered = torch.zeros(world * 8, dtype=torch.int64, device=dev)  # one all-gather target
 
     padd = points_fold(curve)  # the partials' fold: one pm_points_sum call
@@ -451,10 +481,9 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
             "data": "synthetic (SplitMix64 scalars in [0,r), bases [a_i]G generated on device)",
             "config": leg["config"],
-            "kernels_ms": leg["kernels_ms"],
             "roofline": leg.get("roofline"),  # absent only when --logn puts the leg on the small-MSM path
         }
-        for k in ("variable_base", "host_scalars", "dropin_pm_msm", "small_n"):
+        for k in ("kernels_ms", "variable_base", "host_scalars", "dropin_pm_msm", "small_n"):
             if k in leg:
                 out[k] = leg[k]
         if cpu is not None:
@@ -498,6 +527,18 @@ def main():
         emit(out, args.detail)
     if dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(d, result):
+    """--dump-outputs: what the last timed step returned to its caller, the
+    MSM's affine point (x, y: 8 x u64 Montgomery limbs, as best_multiexp
+    returns it), written as DIR/msm_result.npy: its 16 32-bit halves (least
+    significant first) in float64, which holds each of them exactly."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    limbs = np.ascontiguousarray(result, dtype=np.uint64).reshape(8)
+    np.save(os.path.join(d, "msm_result.npy"), limbs.view(np.uint32).astype(np.float64))
 
 
 def settle(step, seconds=0.3):
@@ -621,7 +662,7 @@ def run_msm_leg(args, ctx, dist, dev, world, curve, n, i0, roofline, breakdown, 
     if roofline and launches:
         # one k_accumulate launch consumes all n (scalar, base) pairs of the MSM
         out["roofline"] = roofline_of(n, acc_ms / launches, launches / args.steps, f"{name}_msm_2^{lg}_per_gpu")
-    if roofline:
+    if roofline and args.full:
         out["variable_base"] = run_variable_base(args, ctx, dist, dev, world, curve, d_s, d_b, n, result, name, lg)
     if host_leg and n:
         out["host_scalars"] = run_host_scalars(args, ctx, rb, d_s, n, dist, dev, world, result)

@@ -1,4 +1,5 @@
-"""Generate tests/golden/msm_vectors.npz with the Python oracle (oracle/pasta.py).
+"""Generate tests/golden/msm_vectors.npz and msm_vectors_2.npz (one set of
+cases in two archives) with the Python oracle (oracle/pasta.py).
 
 Every expected value is the oracle's restatement of halo2 best_multiexp and is
 asserted equal to (a) the naive double-and-add sum and (b) the known-discrete-
@@ -17,6 +18,7 @@ import sys
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+SECOND_ARCHIVE = "pallas_equal_scalars."  # the arrays kept in msm_vectors_2.npz
 sys.path.insert(0, os.path.join(HERE, "..", "..", "oracle"))
 import pasta as P  # noqa: E402
 
@@ -89,7 +91,10 @@ def main():
     for n in (1, 33, 1024):
         add(f"bn254_n{n}", 2, sb[:n], pb[:n], ab[:n], "synthetic", check_naive=n <= 33)
 
+    # two archives, each below 1 MiB: the 4096-point giant-bucket case on its own
+    second = {k: cases.pop(k) for k in list(cases) if k.startswith(SECOND_ARCHIVE)}
     np.savez_compressed(os.path.join(HERE, "msm_vectors.npz"), **cases)
+    np.savez_compressed(os.path.join(HERE, "msm_vectors_2.npz"), **second)
     with open(os.path.join(HERE, "msm_vectors.json"), "w") as f:
         json.dump(index, f, indent=1, sort_keys=True)
 

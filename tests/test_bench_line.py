@@ -84,6 +84,41 @@ def test_dry_run_line():
         assert k in line
 
 
+LEG_OPTIONS = ("fixed", "fixed23", "logn22", "strong_logn", "small_n", "ntt_logn", "ntt_large_logn", "accum_batch",
+               "accum_b16", "accum_b32", "accum_large", "inst_batch")
+
+
+def test_plain_run_is_the_headline_alone():
+    """Without --full every other leg, the CPU baselines and the detail file
+    are off, whatever the leg options say; --full keeps their defaults."""
+    for argv in ([], ["--gpus", "1", "--steps", "7", "--warmup", "2"], ["--accum-large", "4096", "--logn22", "1"]):
+        a = bench.parse(argv)
+        assert not a.full and a.no_cpu and a.detail == ""
+        assert all(getattr(a, k) == 0 for k in LEG_OPTIONS), argv
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.gpus, a.logn) == (7, 2, 1, 20)
+    f = bench.parse(["--full"])
+    assert f.full and not f.no_cpu and f.detail == bench.DETAIL_DEFAULT
+    assert all(getattr(f, k) > 0 for k in LEG_OPTIONS)
+    assert bench.parse(["--full", "--detail", ""]).detail == ""
+    assert bench.parse(["--detail", "x.json"]).detail == "x.json"
+
+
+def test_dump_outputs_holds_the_limbs_exactly(tmp_path):
+    """--dump-outputs: the result point's 8 u64 limbs as 16 32-bit halves in
+    float64, exact for every limb value."""
+    import numpy as np
+
+    limbs = np.array([0, 1, 2**32 - 1, 2**32, 2**53 + 1, 2**64 - 1, 0x0123456789ABCDEF, 0xFEDCBA9876543210],
+                     dtype=np.uint64)
+    d = tmp_path / "out"
+    bench.dump_outputs(str(d), limbs)
+    got = np.load(d / "msm_result.npy")
+    assert got.dtype == np.float64 and got.shape == (16,)
+    back = got[0::2].astype(np.uint64) | (got[1::2].astype(np.uint64) << np.uint64(32))
+    assert np.array_equal(back, limbs)
+
+
 def test_final_record_host_scalar_legs():
     """The final round-6 record (the split scalar copy): the host-scalar legs'
     summaries carry the one-copy comparison, and the whole line compacts

@@ -2,7 +2,7 @@
 # Round-4 GPU session (through gpurun, from the repo root): bash tools/gpu_r04.sh TAG [parts]
 #   test   pytest -m gpu (one process) [TESTS="tests/x.py ..." to restrict, K="expr" for -k]
 #   smoke  __graft_entry__.smoke()
-#   bench  the default bench.py line -> bench.json
+#   bench  the bench.py --full line -> bench.json
 #   quick  headline + accumulator legs only -> bench_quick.json
 #   kt     rocprofv3 --kernel-trace --stats of the headline-only bench
 #   acckt  rocprofv3 --kernel-trace --stats of the accumulator-only bench
@@ -29,18 +29,18 @@ for P in $PARTS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
       cat $OUT/smoke.log ;;
     bench)
-      timeout -k 10 900 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+      timeout -k 10 900 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
       cut -c1-400 $OUT/bench.json ;;
     quick)
-      timeout -k 10 600 python -u bench.py --no-cpu $QUICK > $OUT/bench_quick.json 2> $OUT/bench_quick.err || { tail -20 $OUT/bench_quick.err; exit 1; }
+      timeout -k 10 600 python -u bench.py --full --no-cpu $QUICK > $OUT/bench_quick.json 2> $OUT/bench_quick.err || { tail -20 $OUT/bench_quick.err; exit 1; }
       cut -c1-400 $OUT/bench_quick.json ;;
     kt)
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/kt -o run -- python3 bench.py --no-cpu \
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/kt -o run -- python3 bench.py --full --no-cpu \
         $QUICK --accum-batch 0 --accum-b16 0 > $OUT/kt.log 2>&1 || { echo "kernel trace failed"; tail -20 $OUT/kt.log; exit 1; }
       find $OUT/kt -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats.csv \;
       cut -c1-150 $OUT/kernel_stats.csv | head -14 ;;
     acckt)
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/acckt -o run -- python3 bench.py --no-cpu \
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/acckt -o run -- python3 bench.py --full --no-cpu \
         $QUICK --logn 15 --accum-b16 1 > $OUT/acckt.log 2>&1 || { echo "kernel trace failed"; tail -20 $OUT/acckt.log; exit 1; }
       find $OUT/acckt -name '*kernel_stats.csv' -exec cp {} $OUT/acc_kernel_stats.csv \;
       cut -c1-150 $OUT/acc_kernel_stats.csv | head -20 ;;
