@@ -96,8 +96,11 @@ def test_fixed_vs_variable_random(gpu_ctx, curve):
 
 def test_fixed_known_dlog_2_20(gpu_ctx):
     """2^20 Pallas fixed-base MSM == the variable-base MSM == [sum s_i a_i]G
-    (the latter is checked in test_msm_gpu.test_known_dlog_2_20)."""
+    (the variable-base MSM against that point also: test_msm_gpu.test_known_dlog);
+    with every scalar equal, both == the C port of best_multiexp."""
     import torch
+
+    from dlog_util import known_dlog_point
 
     n = 1 << 20
     dev = torch.device("cuda", gpu_ctx.device)
@@ -107,11 +110,14 @@ def test_fixed_known_dlog_2_20(gpu_ctx):
     gpu_ctx.synth_bases(0, P.SEED_BASES, 0, n, b.data_ptr())
     torch.cuda.synchronize()
     want = gpu_ctx.msm_device(0, s.data_ptr(), b.data_ptr(), n)
+    assert P.limbs_to_point(P.PALLAS, [int(x) for x in want]) == known_dlog_point(0, n)
     fb = gpu_ctx.fixed_bases(0, d_bases=b.data_ptr(), n=n)
     try:
         assert np.array_equal(fb.msm_device(s.data_ptr(), n), want)
         s[:] = s[3]   # one bucket per window: long fixup chains in the merged bucket set
         want2 = gpu_ctx.msm_device(0, s.data_ptr(), b.data_ptr(), n)
+        assert np.array_equal(want2, msm_ref.best_multiexp(0, s.cpu().numpy().view(np.uint64),
+                                                           b.cpu().numpy().view(np.uint64)))
         assert np.array_equal(fb.msm_device(s.data_ptr(), n), want2)
     finally:
         fb.release()
@@ -191,6 +197,9 @@ def test_fixed_rows2_vs_variable(gpu_ctx, curve):
     b[n - 5] = 0
     torch.cuda.synchronize()
     want = gpu_ctx.msm_device(curve, s.data_ptr(), b.data_ptr(), n)
+    # the expected value itself against the C port of best_multiexp (identity rows included)
+    assert np.array_equal(want, msm_ref.best_multiexp(curve, s.cpu().numpy().view(np.uint64),
+                                                      b.cpu().numpy().view(np.uint64)))
     fb = gpu_ctx.fixed_bases(curve, d_bases=b.data_ptr(), n=n, c=16, rows=2)
     try:
         assert fb.windows == 16 and fb.table_bytes >= 2 * n * 64

@@ -248,8 +248,7 @@ def test_resident_device_and_host_paths(gpu_ctx, curve, n):
     finally:
         rb.release()
         rh.release()
-    if n < (1 << 20):
-        assert np.array_equal(want, msm_ref.best_multiexp(curve, S, B))
+    assert np.array_equal(want, msm_ref.best_multiexp(curve, S, B))
 
 
 @pytest.mark.parametrize("k", [1, 2, 5])
@@ -301,6 +300,9 @@ def test_resident_row_table(gpu_ctx, curve):
     rb = gpu_ctx.upload_bases(curve, d_bases=b.data_ptr(), n=n)
     try:
         want = gpu_ctx.msm_device(curve, s.data_ptr(), b.data_ptr(), n)
+        # the expected value itself against the C port of best_multiexp
+        assert np.array_equal(want, msm_ref.best_multiexp(curve, s.cpu().numpy().view(np.uint64),
+                                                          b.cpu().numpy().view(np.uint64)))
         assert np.array_equal(gpu_ctx.msm_resident_device(rb, 0, s.data_ptr(), n), want)
         m = (1 << 19) + 17   # covers more than half of the table: row-table path
         assert np.array_equal(gpu_ctx.msm_resident_device(rb, 0, s.data_ptr(), m),
@@ -427,6 +429,7 @@ def test_dropin_row_table(gpu_ctx):
     want = gpu_ctx.msm_device(0, s.data_ptr(), b.data_ptr(), n)
     S = s.cpu().numpy().view(np.uint64).copy()
     B = b.cpu().numpy().view(np.uint64).copy()
+    assert np.array_equal(want, msm_ref.best_multiexp(0, S, B))   # the expected value against the C port
     ctx = H.Context(0)
     try:
         for _ in range(4):
@@ -468,11 +471,20 @@ def test_split_scalar_copy(gpu_ctx, curve):
     n = (1 << 19) + 8195
     s, b = _torch_inputs(gpu_ctx, curve, n)
     S = s.cpu().numpy().view(np.uint64).copy()
+    B = b.cpu().numpy().view(np.uint64).copy()
+    C = P.CURVES[curve]
+
+    def as_point(v):
+        return P.limbs_to_point(C, [int(x) for x in v])
+
     rb = gpu_ctx.upload_bases(curve, d_bases=b.data_ptr(), n=n)
     try:
         assert rb.rows > 1
         for m in (n, (1 << 19) + 17, n - 8192):   # > n / 2: the row-table path
             want = gpu_ctx.msm_resident_device(rb, 0, s.data_ptr(), m)
+            # every expected value below: also against the C port of best_multiexp
+            assert np.array_equal(want, msm_ref.best_multiexp(curve, S[:m], B[:m])), m
+            assert as_point(want) == known_dlog_point(curve, m), m
             assert np.array_equal(gpu_ctx.msm_resident(rb, 0, S[:m]), want), m
             gpu_ctx.set_msm_option(H.MSM_OPT_SPLIT_COPY, 0)
             try:
@@ -481,12 +493,15 @@ def test_split_scalar_copy(gpu_ctx, curve):
                 gpu_ctx.set_msm_option(H.MSM_OPT_SPLIT_COPY, -1)
         # canonical scalars (PM_SCALARS_CANONICAL) through both parts
         want = gpu_ctx.msm_resident_device(rb, 0, s.data_ptr(), n, canonical=True)
+        assert np.array_equal(want, msm_ref.best_multiexp(curve, S, B, canonical=True))
         assert np.array_equal(gpu_ctx.msm_resident(rb, 0, S, canonical=True), want)
         # every scalar equal: one giant bucket per window, in both parts' lists
         e = s[7:8].repeat(n, 1).contiguous()
         torch.cuda.synchronize()
         want = gpu_ctx.msm_resident_device(rb, 0, e.data_ptr(), n)
-        assert np.array_equal(gpu_ctx.msm_resident(rb, 0, e.cpu().numpy().view(np.uint64).copy()), want)
+        Eq = e.cpu().numpy().view(np.uint64).copy()
+        assert np.array_equal(want, msm_ref.best_multiexp(curve, Eq, B))
+        assert np.array_equal(gpu_ctx.msm_resident(rb, 0, Eq), want)
     finally:
         rb.release()
     # at the threshold: a fresh table of exactly PM_SPLIT_COPY_MIN_N (+ 1) points
@@ -495,6 +510,8 @@ def test_split_scalar_copy(gpu_ctx, curve):
         try:
             assert rb.rows > 1
             want = gpu_ctx.msm_resident_device(rb, 0, s.data_ptr(), m)
+            assert np.array_equal(want, msm_ref.best_multiexp(curve, S[:m], B[:m])), m
+            assert as_point(want) == known_dlog_point(curve, m), m
             assert np.array_equal(gpu_ctx.msm_resident(rb, 0, S[:m]), want), m
         finally:
             rb.release()
@@ -506,6 +523,8 @@ def test_split_scalar_copy(gpu_ctx, curve):
     rb = gpu_ctx.upload_bases(curve, d_bases=b3.data_ptr(), n=m)
     try:
         want = gpu_ctx.msm_resident_device(rb, 0, s3.data_ptr(), m)
+        assert np.array_equal(want, msm_ref.best_multiexp(curve, S3, b3.cpu().numpy().view(np.uint64)))
+        assert as_point(want) == known_dlog_point(curve, m)
         assert np.array_equal(gpu_ctx.msm_resident(rb, 0, S3), want)
     finally:
         rb.release()
@@ -520,7 +539,9 @@ def test_split_scalar_copy(gpu_ctx, curve):
     m = (1 << 18) + 5
     fb = gpu_ctx.fixed_bases(curve, d_bases=b.data_ptr(), n=m)
     try:
-        assert np.array_equal(fb.msm(S[:m]), gpu_ctx.msm_device(curve, s.data_ptr(), b.data_ptr(), m))
+        want = gpu_ctx.msm_device(curve, s.data_ptr(), b.data_ptr(), m)
+        assert np.array_equal(want, msm_ref.best_multiexp(curve, S[:m], B[:m]))
+        assert np.array_equal(fb.msm(S[:m]), want)
     finally:
         fb.release()
 
