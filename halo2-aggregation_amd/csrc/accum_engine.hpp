@@ -906,6 +906,7 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
 
 #include "ntt_engine.hpp"  // uses fe_from_u64 above
 #include "msm_many.hpp"
+#include "poly_engine.hpp"
 
 // Explicit instantiations are visible to both compilation passes, so the
 // device pass instantiates every kernel the host driver launches; the op
@@ -922,7 +923,8 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
                          &fixed_table_impl<Cv>, &ntt_device_impl<Cv>, &msm_fixed_to_aff<Cv>,    \
                          &bases_to29_impl<Cv>, &msm_resident_batch_impl<Cv>, &proofs_device_impl<Cv>,    \
                          &msm_start_impl<Cv>, &msm_finish_impl<Cv>, &msm_small_impl<Cv>,         \
-                         &many_table_impl<Cv>, &msm_many_impl<Cv>, &points_sum_impl<typename Cv::Base>};
+                         &many_table_impl<Cv>, &msm_many_impl<Cv>, &points_sum_impl<typename Cv::Base>, \
+                         &poly_eval_impl<Cv>, &poly_witness_impl<Cv>};
 #endif
 #define PM_DEFINE_CURVE_OPS(Cv, name)                                                          \
   namespace pm {                                                                               \
@@ -950,5 +952,9 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
   template int many_table_impl<Cv>(Ctx*, const void*, size_t, ManyTable*);                       \
   template int msm_many_impl<Cv>(Ctx*, const ManyTable*, size_t, const size_t*, const size_t*, const void*, bool, \
                                  uint32_t, uint64_t*);                                           \
+  template int poly_eval_impl<Cv>(Ctx*, const void* const*, size_t, size_t, const uint32_t*, const uint64_t*, size_t, \
+                                  uint64_t*);                                                    \
+  template int poly_witness_impl<Cv>(Ctx*, const void* const*, size_t, size_t, const uint32_t*, const uint32_t*, \
+                                     const uint64_t*, const uint64_t*, size_t, void*, uint64_t*); \
   PM_OPS_TABLE(Cv, name)                                                                       \
   }

@@ -697,12 +697,20 @@ int pm_bases_release(pm_bases* b) {
   return PM_OK;
 }
 
+static int msm_resident_locked(pm_ctx* ctx, const pm_bases* b, size_t offset, const void* scalars, bool host,
+                               size_t n, uint32_t flags, uint64_t out[8]);
 static int msm_resident(pm_ctx* ctx, const pm_bases* b, size_t offset, const void* scalars, bool host, size_t n,
                         uint32_t flags, uint64_t out[8]) {
   if (!ctx || !b || !out || (n && !scalars)) return set_error(PM_ERR_ARG, "null argument");
   if (b->device != ctx->device) return set_error(PM_ERR_ARG, "bases live on another device");
   if (offset > b->n || n > b->n - offset) return set_error(PM_ERR_ARG, "window exceeds resident bases");
   std::lock_guard<std::mutex> lk(ctx->mu);
+  return msm_resident_locked(ctx, b, offset, scalars, host, n, flags, out);
+}
+
+// arguments validated, ctx->mu held (pm_multiopen_open_device commits its quotient rows under one lock)
+static int msm_resident_locked(pm_ctx* ctx, const pm_bases* b, size_t offset, const void* scalars, bool host,
+                               size_t n, uint32_t flags, uint64_t out[8]) {
   if (n == 0) {
     std::memset(out, 0, 64);
     return PM_OK;
@@ -1229,6 +1237,135 @@ int pm_fft(pm_ctx* ctx, int curve, uint64_t* data, uint32_t log_n, const uint64_
   if ((rc = ops->ntt(ctx, curve, ctx->in_scalars.p, log_n, omega, scale))) return rc;
   HIP_TRY(hipMemcpyAsync(data, ctx->in_scalars.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
+// ------------------------------------------------- polynomial openings (§8f-5)
+// As everywhere in this file, an error after begin_call() returns at once (a
+// failed ensure / HIP call, or an MSM failing between the witness and the
+// commits of pm_multiopen_open_device): the context's per-call state is reset
+// by the next begin_call(), and the outputs of the failed call are unspecified.
+namespace {
+// shared checks of the evaluation / witness entries; everything here runs before the device is touched
+int poly_check_common(pm_ctx* ctx, int curve, const void* const* d_polys, size_t P, size_t n, const CurveOps** ops) {
+  if (!ctx || !d_polys) return set_error(PM_ERR_ARG, "null argument");
+  if (!(*ops = curve_ops(curve))) return set_error(PM_ERR_ARG, "unknown curve id");
+  if (n == 0) return set_error(PM_ERR_ARG, "empty polynomial");
+  for (size_t i = 0; i < P; i++)
+    if (!d_polys[i]) return set_error(PM_ERR_ARG, "null polynomial pointer");
+  return PM_OK;
+}
+
+int witness_check(pm_ctx* ctx, int curve, const void* const* d_polys, size_t P, size_t n, const uint32_t* set_offsets,
+                  const uint32_t* set_polys, const uint64_t* points, const uint64_t* v, size_t S, size_t max_n,
+                  const CurveOps** ops) {
+  int rc = poly_check_common(ctx, curve, d_polys, P, n, ops);
+  if (rc) return rc;
+  if (S == 0) return PM_OK;
+  if (!set_offsets || !set_polys || !points || !v) return set_error(PM_ERR_ARG, "null argument");
+  if (set_offsets[0] != 0) return set_error(PM_ERR_ARG, "set_offsets[0] must be 0");
+  for (size_t j = 0; j < S; j++) {
+    if (set_offsets[j + 1] <= set_offsets[j]) return set_error(PM_ERR_ARG, "a rotation set has no polynomial");
+    for (uint32_t i = set_offsets[j]; i < set_offsets[j + 1]; i++)
+      if (set_polys[i] >= P) return set_error(PM_ERR_ARG, "polynomial index out of range");
+  }
+  if (n > max_n)
+    return set_error(PM_ERR_UNSUPPORTED, max_n == pm::kMaxPoints ? "opening longer than 2^26 (the MSM's limit)"
+                                                                   : "polynomial longer than 2^28");
+  if (S > pm::kPolyMaxGridY) return set_error(PM_ERR_UNSUPPORTED, "more than 65535 rotation sets in one call");
+  return PM_OK;
+}
+}  // namespace
+
+int pm_poly_eval_device(pm_ctx* ctx, int curve, const void* const* d_polys, size_t P, size_t n,
+                        const uint32_t* poly_index, const uint64_t* points, size_t E, uint64_t* out_evals) {
+  const CurveOps* ops = nullptr;
+  int rc = poly_check_common(ctx, curve, d_polys, P, n, &ops);
+  if (rc) return rc;
+  if (E == 0) return PM_OK;
+  if (!poly_index || !points || !out_evals) return set_error(PM_ERR_ARG, "null argument");
+  for (size_t e = 0; e < E; e++)
+    if (poly_index[e] >= P) return set_error(PM_ERR_ARG, "polynomial index out of range");
+  if (n > pm::kPolyMaxN) return set_error(PM_ERR_UNSUPPORTED, "polynomial longer than 2^28");
+  if (E > pm::kPolyMaxGridY) return set_error(PM_ERR_UNSUPPORTED, "more than 65535 evaluations in one call");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if ((rc = ctx->begin_call())) return rc;
+  return ops->poly_eval(ctx, d_polys, P, n, poly_index, points, E, out_evals);
+}
+
+int pm_multiopen_witness_device(pm_ctx* ctx, int curve, const void* const* d_polys, size_t P, size_t n,
+                                const uint32_t* set_offsets, const uint32_t* set_polys, const uint64_t* points,
+                                const uint64_t v[4], size_t S, void* d_out_quotients, uint64_t* out_evals) {
+  const CurveOps* ops = nullptr;
+  int rc = witness_check(ctx, curve, d_polys, P, n, set_offsets, set_polys, points, v, S, pm::kPolyMaxN, &ops);
+  if (rc) return rc;
+  if (S == 0) return PM_OK;
+  if (!d_out_quotients) return set_error(PM_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if ((rc = ctx->begin_call())) return rc;
+  return ops->poly_witness(ctx, d_polys, P, n, set_offsets, set_polys, points, v, S, d_out_quotients, out_evals);
+}
+
+int pm_multiopen_open_device(pm_ctx* ctx, int curve, const void* const* d_polys, size_t P, size_t n,
+                             const uint32_t* set_offsets, const uint32_t* set_polys, const uint64_t* points,
+                             const uint64_t v[4], size_t S, const pm_bases* srs, uint64_t* out_w,
+                             uint64_t* out_evals) {
+  const CurveOps* ops = nullptr;
+  int rc = witness_check(ctx, curve, d_polys, P, n, set_offsets, set_polys, points, v, S, pm::kMaxPoints, &ops);
+  if (rc) return rc;
+  if (!srs) return set_error(PM_ERR_ARG, "null argument");
+  if (S == 0) return PM_OK;
+  if (!out_w) return set_error(PM_ERR_ARG, "null argument");
+  if (srs->curve != curve) return set_error(PM_ERR_ARG, "the SRS belongs to another curve");
+  if (srs->device != ctx->device) return set_error(PM_ERR_ARG, "bases live on another device");
+  if (n > srs->n) return set_error(PM_ERR_ARG, "the SRS is shorter than the polynomials");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if ((rc = ctx->begin_call())) return rc;
+  if ((rc = ctx->poly_q.ensure(S * n * 32))) return rc;
+  if ((rc = ops->poly_witness(ctx, d_polys, P, n, set_offsets, set_polys, points, v, S, ctx->poly_q.p, out_evals)))
+    return rc;
+  for (size_t j = 0; j < S; j++)
+    if ((rc = msm_resident_locked(ctx, srs, 0, (const char*)ctx->poly_q.p + j * n * 32, false, n, 0, out_w + 8 * j)))
+      return rc;
+  return PM_OK;
+}
+
+int pm_eval_polynomial(pm_ctx* ctx, int curve, const uint64_t* coeffs, size_t n, const uint64_t point[4],
+                       uint64_t out[4]) {
+  if (!ctx || !coeffs || !point || !out) return set_error(PM_ERR_ARG, "null argument");
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return set_error(PM_ERR_ARG, "unknown curve id");
+  if (n == 0) return set_error(PM_ERR_ARG, "empty polynomial");
+  if (n > pm::kPolyMaxN) return set_error(PM_ERR_UNSUPPORTED, "polynomial longer than 2^28");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = ctx->begin_call();
+  if (rc) return rc;
+  if ((rc = ctx->in_scalars.ensure(n * 32))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->in_scalars.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  const void* poly = ctx->in_scalars.p;
+  const uint32_t index = 0;
+  return ops->poly_eval(ctx, &poly, 1, n, &index, point, 1, out);
+}
+
+int pm_kate_division(pm_ctx* ctx, int curve, const uint64_t* coeffs, size_t n, const uint64_t z[4], uint64_t* out_q) {
+  if (!ctx || !coeffs || !z || (n > 1 && !out_q)) return set_error(PM_ERR_ARG, "null argument");
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return set_error(PM_ERR_ARG, "unknown curve id");
+  if (n == 0) return set_error(PM_ERR_ARG, "empty polynomial");
+  if (n > pm::kPolyMaxN) return set_error(PM_ERR_UNSUPPORTED, "polynomial longer than 2^28");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = ctx->begin_call();
+  if (rc) return rc;
+  if ((rc = ctx->in_scalars.ensure(n * 32)) || (rc = ctx->poly_q.ensure(n * 32))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->in_scalars.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  const void* poly = ctx->in_scalars.p;
+  const uint32_t offsets[2] = {0, 1}, index = 0;
+  // one set of one polynomial: v does not enter (any value serves)
+  if ((rc = ops->poly_witness(ctx, &poly, 1, n, offsets, &index, z, z, 1, ctx->poly_q.p, nullptr))) return rc;
+  if (n > 1) {
+    HIP_TRY(hipMemcpyAsync(out_q, ctx->poly_q.p, (n - 1) * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
   return PM_OK;
 }
 

@@ -199,6 +199,12 @@ inline uint32_t many_pick_c(size_t n) {
 }
 constexpr size_t kNttTwiddleSlots = 4;
 constexpr uint32_t kNttMaxLog = 28;  // pm_fft: three passes above 2^22; BN254 Fr has 2-adicity 28
+// polynomial openings (poly_engine.hpp)
+// longest polynomial: k_poly_table keeps 29 slots of z^(2^k) (a call at 2^28
+// reads k <= 20, poly_table_squarings) and the tile index is grid.x (2^17
+// tiles of 2^11 at 2^28); the limit matches pm_fft's, the scan needs no more
+constexpr size_t kPolyMaxN = size_t(1) << 28;
+constexpr size_t kPolyMaxGridY = 65535;        // sets / pairs per call (grid.y)
 struct NttTwiddles {
   int curve = -1;
   uint32_t logn = 0;
@@ -259,6 +265,8 @@ struct pm_ctx {
   pm::Buf in_scalars, in_scalars2, in_bases, digits, sorted, counts, offsets, cursor, bsum, buckets, head, segS, segT, bits,
       win, longs, mid, acc_coef, acc_part, acc_io, bases29, tr_io, bitsP, tickets, ntt_scratch, bitsQ, acc_lad, acc_corr, tr_canon, ntt_scratch2,
       acc_vkpow, small_tab, small_dig, small_part, small_tk;
+  // polynomial openings (poly_engine.hpp): per-call upload, power tables, scan scratch, quotient rows of pm_multiopen_open*
+  pm::Buf poly_job, poly_tab, poly_aux, poly_q;
   // the later parts' sorted lists and bucket partials of the split scalar
   // copy (engine.hpp; the sort scratch is shared, its kernels run in order)
   pm::Buf part_sorted[2], part_offsets[2], part_buckets[2], part_head[2];
@@ -297,7 +305,7 @@ struct pm_ctx {
   std::vector<pm::Buf*> all_bufs() {
     return {&in_scalars, &in_scalars2, &in_bases, &digits, &sorted, &counts, &offsets, &cursor,
             &bsum,       &buckets,  &head,   &segS,   &segT,   &bits,    &win, &longs, &mid,
-            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1]};
+            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1], &poly_job, &poly_tab, &poly_aux, &poly_q};
   }
   ~pm_ctx();
   int begin_call();
@@ -371,6 +379,13 @@ struct CurveOps {
                   bool s_host, uint32_t flags, uint64_t* out);
   // host: out = sum of n affine points (XYZZ accumulation, one inversion)
   int (*points_sum)(const uint64_t* points, size_t n, uint64_t out[8]);
+  // polynomial openings (poly_engine.hpp): E (polynomial, point) evaluations;
+  // the S witness quotients of a multiopen argument (+ batched evaluations)
+  int (*poly_eval)(Ctx* ctx, const void* const* d_polys, size_t P, size_t n, const uint32_t* poly_index,
+                   const uint64_t* points, size_t E, uint64_t* out_evals);
+  int (*poly_witness)(Ctx* ctx, const void* const* d_polys, size_t P, size_t n, const uint32_t* set_offsets,
+                      const uint32_t* set_polys, const uint64_t* points, const uint64_t* v, size_t S, void* d_out,
+                      uint64_t* out_evals);
 };
 extern const CurveOps kPallasOps, kVestaOps, kBn254Ops;
 

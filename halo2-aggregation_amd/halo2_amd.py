@@ -297,6 +297,15 @@ def _load():
         "pm_msm_fixed_device": ([_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_uint32, _u64p], ctypes.c_int),
         "pm_fft": ([_vp, ctypes.c_int, _u64p, ctypes.c_uint32, _u64p, _u64p], ctypes.c_int),
         "pm_fft_device": ([_vp, ctypes.c_int, _vp, ctypes.c_uint32, _u64p, _u64p], ctypes.c_int),
+        "pm_poly_eval_device": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_size_t, ctypes.c_size_t, _u32p,
+                                 _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
+        "pm_multiopen_witness_device": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_size_t, ctypes.c_size_t,
+                                         _u32p, _u32p, _u64p, _u64p, ctypes.c_size_t, _vp, _u64p], ctypes.c_int),
+        "pm_multiopen_open_device": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_size_t, ctypes.c_size_t,
+                                      _u32p, _u32p, _u64p, _u64p, ctypes.c_size_t, _vp, _u64p, _u64p],
+                                     ctypes.c_int),
+        "pm_eval_polynomial": ([_vp, ctypes.c_int, _u64p, ctypes.c_size_t, _u64p, _u64p], ctypes.c_int),
+        "pm_kate_division": ([_vp, ctypes.c_int, _u64p, ctypes.c_size_t, _u64p, _u64p], ctypes.c_int),
         "pm_vk_transcript_repr": ([ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, _u64p], ctypes.c_int),
         "pm_transcript_batch": ([_vp, ctypes.c_int, ctypes.POINTER(PmProofShape), ctypes.c_size_t, _u64p, _u64p,
                                  _u64p, _u64p, _u32p], ctypes.c_int),
@@ -883,6 +892,95 @@ class Context:
         w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.uint64).reshape(4)
         _check(lib().pm_fft_device(self.h, curve, _vp(d_data), log_n, _p(w), None if sc is None else _p(sc)))
+
+    # ---- polynomial openings (pm_poly_eval* / pm_multiopen_*): d_polys is a
+    # sequence of device pointers, each to n Montgomery scalars
+    @staticmethod
+    def _poly_ptrs(d_polys):
+        ptrs = [int(p) for p in d_polys]
+        return (_vp * max(1, len(ptrs)))(*ptrs), len(ptrs)
+
+    @staticmethod
+    def _open_args(sets, points, v):
+        """sets: one sequence of polynomial indices per rotation set, in query
+        order; points (S, 4); v (4,)."""
+        sets = [[int(i) for i in s] for s in sets]
+        z = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        if z.shape[0] != len(sets):
+            raise ValueError("one point per rotation set")
+        vv = np.ascontiguousarray(v, dtype=np.uint64).reshape(-1)
+        if vv.shape[0] != 4:
+            raise ValueError("v must be one scalar (4 x u64)")
+        offs = np.zeros(len(sets) + 1, dtype=np.uint32)
+        offs[1:] = np.cumsum([len(s) for s in sets], dtype=np.uint64)
+        flat = np.array([i for s in sets for i in s] or [0], dtype=np.uint32)
+        if not z.shape[0]:
+            z = np.zeros((1, 4), dtype=np.uint64)
+        return offs, flat, z, vv, len(sets)
+
+    def poly_eval_device(self, curve, d_polys, n, poly_index, points):
+        """pm_poly_eval_device: out[e] = p_{poly_index[e]}(points[e]);
+        poly_index (E,), points (E, 4) u64 Montgomery -> (E, 4)."""
+        idx = np.ascontiguousarray(poly_index, dtype=np.uint32).reshape(-1)
+        z = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        if z.shape[0] != idx.shape[0]:
+            raise ValueError("poly_index and points differ in length")
+        E = idx.shape[0]
+        ptrs, P = self._poly_ptrs(d_polys)
+        out = np.zeros((E, 4), dtype=np.uint64)
+        if E == 0:
+            idx, z = np.zeros(1, dtype=np.uint32), np.zeros((1, 4), dtype=np.uint64)
+        _check(lib().pm_poly_eval_device(self.h, curve, ptrs, P, n, idx.ctypes.data_as(_u32p), _p(z), E,
+                                         _p(out) if E else None))
+        return out
+
+    def multiopen_witness_device(self, curve, d_polys, n, sets, points, v, d_out_quotients, want_evals=True):
+        """pm_multiopen_witness_device: row j of d_out_quotients (S x n scalars
+        on the device) = kate_division(sum_i v^{m-1-i} p_{sets[j][i]},
+        points[j]) and a zero; returns the batched evaluations (S, 4) (None
+        with want_evals=False)."""
+        offs, flat, z, vv, S = self._open_args(sets, points, v)
+        ptrs, P = self._poly_ptrs(d_polys)
+        ev = np.zeros((S, 4), dtype=np.uint64) if want_evals else None
+        _check(lib().pm_multiopen_witness_device(self.h, curve, ptrs, P, n, offs.ctypes.data_as(_u32p),
+                                                 flat.ctypes.data_as(_u32p), _p(z), _p(vv), S,
+                                                 _vp(d_out_quotients), _p(ev) if want_evals and S else None))
+        return ev
+
+    def multiopen_open_device(self, curve, d_polys, n, sets, points, v, srs: Bases):
+        """pm_multiopen_open_device: the witness commitments W_j (S, 8) affine
+        over srs[0, n) and the batched evaluations (S, 4)."""
+        offs, flat, z, vv, S = self._open_args(sets, points, v)
+        ptrs, P = self._poly_ptrs(d_polys)
+        w = np.zeros((S, 8), dtype=np.uint64)
+        ev = np.zeros((S, 4), dtype=np.uint64)
+        _check(lib().pm_multiopen_open_device(self.h, curve, ptrs, P, n, offs.ctypes.data_as(_u32p),
+                                              flat.ctypes.data_as(_u32p), _p(z), _p(vv), S, srs.h,
+                                              _p(w) if S else None, _p(ev) if S else None))
+        return w, ev
+
+    def eval_polynomial(self, curve, coeffs, point):
+        """pm_eval_polynomial (halo2 eval_polynomial): coeffs (n, 4), point
+        (4,) u64 Montgomery -> (4,).  Two PCIe crossings: parity, not speed."""
+        a = _as_u64(coeffs, 4)
+        z = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)
+        if z.shape[0] != 4:
+            raise ValueError("point must be one scalar (4 x u64)")
+        out = np.zeros(4, dtype=np.uint64)
+        _check(lib().pm_eval_polynomial(self.h, curve, _p(a), a.shape[0], _p(z), _p(out)))
+        return out
+
+    def kate_division(self, curve, coeffs, z):
+        """pm_kate_division (halo2 kate_division): the n - 1 quotient
+        coefficients of a(X) / (X - z) -> (n - 1, 4)."""
+        a = _as_u64(coeffs, 4)
+        zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1)
+        if zz.shape[0] != 4:
+            raise ValueError("z must be one scalar (4 x u64)")
+        n = a.shape[0]
+        out = np.zeros((max(n, 1) - 1, 4), dtype=np.uint64)
+        _check(lib().pm_kate_division(self.h, curve, _p(a), n, _p(zz), _p(out) if n > 1 else None))
+        return out
 
     def selftest_field(self, curve, seed, n):
         m = ctypes.c_uint64(0)

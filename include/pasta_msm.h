@@ -474,6 +474,68 @@ int pm_fft(pm_ctx* ctx, int curve, uint64_t* data, uint32_t log_n, const uint64_
 int pm_fft_device(pm_ctx* ctx, int curve, void* d_data, uint32_t log_n, const uint64_t omega[4],
                   const uint64_t* scale);
 
+/* ---- Polynomial openings -------------------------------------
+ * The prover's half of the GWC multiopen argument, between the coefficients
+ * pm_fft_device leaves on the device and the commits of pm_msm_resident*:
+ * halo2 `eval_polynomial(a, x)` = sum_t a_t x^t, `kate_division(a, z)` (the
+ * n - 1 quotient coefficients of a(X) / (X - z): q_{n-2} = a_{n-1},
+ * q_{t-1} = a_t + z q_t; a_0 only enters the remainder a_0 + z q_0 = a(z))
+ * [3P arithmetic.rs], and the witness polynomials of
+ * poly/multiopen/gwc/prover.rs [3P]: for rotation set j with queries
+ * i = 0 .. m_j - 1 at the point z_j,
+ *   batch_j = sum_i v^{m_j-1-i} p_{j,i}    (the order of `f` above)
+ *   q_j     = kate_division(batch_j, z_j)
+ *   W_j     = commit(q_j)
+ * (subtracting the batched evaluation first, as halo2 does, only changes a_0
+ * and so not q_j).  Exact field arithmetic over the scalar field of `curve`;
+ * every scalar is 4 x u64 Montgomery and canonical, like pm_fft's elements,
+ * in and out.
+ *
+ * d_polys is a HOST array of P DEVICE pointers, each to n coefficients.
+ * Index, offset and point arrays, v and the evaluations are host memory.
+ *
+ * pm_poly_eval_device: out_evals[e] = p_{poly_index[e]}(points[e]) for E
+ *   (polynomial, point) pairs in one call; a polynomial may appear under
+ *   several points (its rotations).
+ * pm_multiopen_witness_device: set j uses the polynomials
+ *   set_polys[set_offsets[j] .. set_offsets[j+1]) in query order
+ *   (set_offsets[0] = 0), at points[j].  d_out_quotients is S x n scalars on
+ *   the device: row j holds q_j in elements [0, n-1) and an explicit zero in
+ *   element n-1, so a row is a valid n-term MSM or NTT input.  out_evals
+ *   (S scalars, may be NULL) receives batch_j(z_j) = a_0 + z_j q_0, the batched
+ *   evaluation the verifier's `e` is built from.  An output row must not
+ *   alias an input polynomial.
+ * pm_multiopen_open_device: the same witness into context scratch
+ *   (S x n x 32 B), then S commits over srs[0, n) by the resident MSM path;
+ *   out_w is S affine points, (0,0) for the identity.  Same results as the
+ *   witness call followed by S pm_msm_resident_device calls.
+ * pm_eval_polynomial / pm_kate_division: host-pointer forms in the shape of
+ *   the halo2 functions (copy in, one set of one polynomial, copy out;
+ *   out_q is n - 1 scalars and may be NULL for n == 1).  They pay two PCIe
+ *   crossings: parity, not speed.
+ *
+ * PM_ERR_ARG: a null pointer, an unknown curve, n == 0, a set with no
+ * polynomial, a polynomial index >= P, an SRS shorter than n (checked before
+ * the device is touched).  PM_ERR_UNSUPPORTED: n > 2^28, n > 2^26 for the
+ * open entry (the MSM's limit), more than 65535 sets or pairs in one call.
+ * n == 1 is legal (the quotient row is the single zero, W_j the identity,
+ * out_evals the batched constant).  S == 0 and E == 0 succeed and write
+ * nothing.  Context scratch: 4 n bytes per set (witness), n / 128 bytes per
+ * pair (evaluation). */
+int pm_poly_eval_device(pm_ctx* ctx, int curve, const void* const* d_polys, size_t P, size_t n,
+                        const uint32_t* poly_index, const uint64_t* points, size_t E, uint64_t* out_evals);
+int pm_multiopen_witness_device(pm_ctx* ctx, int curve, const void* const* d_polys, size_t P, size_t n,
+                                const uint32_t* set_offsets, const uint32_t* set_polys, const uint64_t* points,
+                                const uint64_t v[4], size_t S, void* d_out_quotients, uint64_t* out_evals);
+int pm_multiopen_open_device(pm_ctx* ctx, int curve, const void* const* d_polys, size_t P, size_t n,
+                             const uint32_t* set_offsets, const uint32_t* set_polys, const uint64_t* points,
+                             const uint64_t v[4], size_t S, const pm_bases* srs, uint64_t* out_w,
+                             uint64_t* out_evals);
+int pm_eval_polynomial(pm_ctx* ctx, int curve, const uint64_t* coeffs, size_t n, const uint64_t point[4],
+                       uint64_t out[4]);
+int pm_kate_division(pm_ctx* ctx, int curve, const uint64_t* coeffs, size_t n, const uint64_t z[4],
+                     uint64_t* out_q);
+
 /* ---- Blake2b transcript replay ------------------------------
  * The verifier squeezes theta, beta, gamma, y, x, v, u from a halo2
  * Blake2bWrite/Challenge255 transcript (TranscriptChip,
