@@ -1369,6 +1369,94 @@ int pm_kate_division(pm_ctx* ctx, int curve, const uint64_t* coeffs, size_t n, c
   return PM_OK;
 }
 
+// ------------------------------------------------- grand products (§8f-6)
+namespace {
+// everything here runs before the device is touched
+int gp_check(pm_ctx* ctx, int curve, const void* const* d_cols, size_t C, size_t n, const pm_gp_factor* num,
+             const uint32_t* num_offsets, const pm_gp_factor* den, const uint32_t* den_offsets, size_t S,
+             const uint64_t* omega, const uint64_t* start, size_t active, uint32_t flags, const void* d_out_z,
+             const CurveOps** ops) {
+  if (!ctx || !num_offsets || !den_offsets || !start || !d_out_z || (C && !d_cols))
+    return set_error(PM_ERR_ARG, "null argument");
+  if (!(*ops = curve_ops(curve))) return set_error(PM_ERR_ARG, "unknown curve id");
+  if (n == 0) return set_error(PM_ERR_ARG, "empty columns");
+  if (active == 0 || active > n) return set_error(PM_ERR_ARG, "active out of range (1 <= active <= n)");
+  if (S == 0) return set_error(PM_ERR_ARG, "no set");
+  if (flags & ~(uint32_t)PM_GP_CHAIN) return set_error(PM_ERR_ARG, "unknown flag bits");
+  for (size_t i = 0; i < C; i++)
+    if (!d_cols[i]) return set_error(PM_ERR_ARG, "null column pointer");
+  if (n > pm::kPolyMaxN) return set_error(PM_ERR_UNSUPPORTED, "columns longer than 2^28");
+  if (S > pm::kPolyMaxGridY) return set_error(PM_ERR_UNSUPPORTED, "more than 65535 sets in one call");
+  const pm_gp_factor* lists[2] = {num, den};
+  const uint32_t* offs[2] = {num_offsets, den_offsets};
+  for (int l = 0; l < 2; l++) {
+    if (offs[l][0] != 0) return set_error(PM_ERR_ARG, "offsets[0] must be 0");
+    for (size_t j = 0; j < S; j++) {
+      if (offs[l][j + 1] < offs[l][j]) return set_error(PM_ERR_ARG, "offsets must not decrease");
+      if (offs[l][j + 1] - offs[l][j] > PM_GP_MAX_FACTORS)
+        return set_error(PM_ERR_ARG, "more than PM_GP_MAX_FACTORS factors in a list");
+    }
+    if (offs[l][S] && !lists[l]) return set_error(PM_ERR_ARG, "null argument");
+    for (uint32_t i = 0; i < offs[l][S]; i++) {
+      const pm_gp_factor& f = lists[l][i];
+      if (f.x != PM_GP_NONE && f.x >= C) return set_error(PM_ERR_ARG, "column index out of range");
+      if (f.y == PM_GP_OMEGA) {
+        if (!omega) return set_error(PM_ERR_ARG, "a factor names PM_GP_OMEGA and omega is null");
+      } else if (f.y != PM_GP_NONE && f.y >= C) {
+        return set_error(PM_ERR_ARG, "column index out of range");
+      }
+    }
+  }
+  return PM_OK;
+}
+}  // namespace
+
+int pm_grand_product_device(pm_ctx* ctx, int curve, const void* const* d_cols, size_t C, size_t n,
+                            const pm_gp_factor* num, const uint32_t* num_offsets, const pm_gp_factor* den,
+                            const uint32_t* den_offsets, size_t S, const uint64_t omega[4], const uint64_t start[4],
+                            size_t active, uint32_t flags, void* d_out_z, uint64_t* out_last) {
+  const CurveOps* ops = nullptr;
+  int rc = gp_check(ctx, curve, d_cols, C, n, num, num_offsets, den, den_offsets, S, omega, start, active, flags,
+                    d_out_z, &ops);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if ((rc = ctx->begin_call())) return rc;
+  return ops->grand_product(ctx, curve, d_cols, C, n, num, num_offsets, den, den_offsets, S, omega, start, active, flags,
+                            d_out_z, out_last);
+}
+
+int pm_batch_invert_device(pm_ctx* ctx, int curve, void* d_data, size_t n) {
+  if (!ctx || (n && !d_data)) return set_error(PM_ERR_ARG, "null argument");
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return set_error(PM_ERR_ARG, "unknown curve id");
+  if (n == 0) return PM_OK;
+  if (n > pm::kPolyMaxN) return set_error(PM_ERR_UNSUPPORTED, "more than 2^28 values");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = ctx->begin_call();
+  if (rc) return rc;
+  return ops->grand_product(ctx, curve, nullptr, 0, n, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, n,
+                            pm::kGpInvert, d_data, nullptr);
+}
+
+int pm_batch_invert(pm_ctx* ctx, int curve, uint64_t* data, size_t n) {
+  if (!ctx || (n && !data)) return set_error(PM_ERR_ARG, "null argument");
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return set_error(PM_ERR_ARG, "unknown curve id");
+  if (n == 0) return PM_OK;
+  if (n > pm::kPolyMaxN) return set_error(PM_ERR_UNSUPPORTED, "more than 2^28 values");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = ctx->begin_call();
+  if (rc) return rc;
+  if ((rc = ctx->in_scalars.ensure(n * 32))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->in_scalars.p, data, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = ops->grand_product(ctx, curve, nullptr, 0, n, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, n,
+                               pm::kGpInvert, ctx->in_scalars.p, nullptr)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(data, ctx->in_scalars.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
 // ------------------------------------------------- fixed-base MSM (§8f-3)
 static int fixed_create(pm_ctx* ctx, int curve, const void* bases, bool host, size_t n, int c, int rows,
                         pm_fixed_bases** out) {

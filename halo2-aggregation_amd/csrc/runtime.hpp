@@ -205,6 +205,9 @@ constexpr uint32_t kNttMaxLog = 28;  // pm_fft: three passes above 2^22; BN254 F
 // tiles of 2^11 at 2^28); the limit matches pm_fft's, the scan needs no more
 constexpr size_t kPolyMaxN = size_t(1) << 28;
 constexpr size_t kPolyMaxGridY = 65535;        // sets / pairs per call (grid.y)
+// grand products (gp_engine.hpp): the same limits; flag bit of CurveOps::grand_product
+// for the in-place batch inversion (never part of the C-ABI's flags)
+constexpr uint32_t kGpInvert = 0x80000000u;
 struct NttTwiddles {
   int curve = -1;
   uint32_t logn = 0;
@@ -267,6 +270,15 @@ struct pm_ctx {
       acc_vkpow, small_tab, small_dig, small_part, small_tk;
   // polynomial openings (poly_engine.hpp): per-call upload, power tables, scan scratch, quotient rows of pm_multiopen_open*
   pm::Buf poly_job, poly_tab, poly_aux, poly_q;
+  // grand products (gp_engine.hpp): the un-carried suffix products, S rows of n (the rest shares the three above)
+  pm::Buf gp_rows;
+  // the power table of the last omega a grand product named: one prover calls with one omega, and the
+  // table's chain of squarings is pure latency (0.04 ms of a 2^20 call); valid while gp_tab.gen == gp_tab_gen
+  pm::Buf gp_tab;
+  int gp_tab_curve = -1;
+  uint32_t gp_tab_nsq = 0;
+  uint64_t gp_tab_omega[4] = {0, 0, 0, 0};
+  uint64_t gp_tab_gen = ~0ull;
   // the later parts' sorted lists and bucket partials of the split scalar
   // copy (engine.hpp; the sort scratch is shared, its kernels run in order)
   pm::Buf part_sorted[2], part_offsets[2], part_buckets[2], part_head[2];
@@ -305,7 +317,7 @@ struct pm_ctx {
   std::vector<pm::Buf*> all_bufs() {
     return {&in_scalars, &in_scalars2, &in_bases, &digits, &sorted, &counts, &offsets, &cursor,
             &bsum,       &buckets,  &head,   &segS,   &segT,   &bits,    &win, &longs, &mid,
-            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1], &poly_job, &poly_tab, &poly_aux, &poly_q};
+            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1], &poly_job, &poly_tab, &poly_aux, &poly_q, &gp_rows, &gp_tab};
   }
   ~pm_ctx();
   int begin_call();
@@ -386,6 +398,12 @@ struct CurveOps {
   int (*poly_witness)(Ctx* ctx, const void* const* d_polys, size_t P, size_t n, const uint32_t* set_offsets,
                       const uint32_t* set_polys, const uint64_t* points, const uint64_t* v, size_t S, void* d_out,
                       uint64_t* out_evals);
+  // grand products and the batch inversion (gp_engine.hpp; flags: PM_GP_CHAIN,
+  // or pm::kGpInvert for the in-place inversion of the n values at d_out)
+  int (*grand_product)(Ctx* ctx, int curve, const void* const* d_cols, size_t C, size_t n, const pm_gp_factor* num,
+                       const uint32_t* num_off, const pm_gp_factor* den, const uint32_t* den_off, size_t S,
+                       const uint64_t* omega, const uint64_t* start, size_t active, uint32_t flags, void* d_out,
+                       uint64_t* out_last);
 };
 extern const CurveOps kPallasOps, kVestaOps, kBn254Ops;
 

@@ -64,6 +64,18 @@ class PmPermColumn(ctypes.Structure):
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 
 
+# pm_grand_product_device (include/pasta_msm.h)
+GP_NONE = 0xFFFFFFFF
+GP_OMEGA = 0xFFFFFFFE
+GP_CHAIN = 1
+GP_MAX_FACTORS = 16
+
+
+class PmGpFactor(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("b", ctypes.c_uint64 * 4),
+                ("g", ctypes.c_uint64 * 4)]
+
+
 class PmProofShape(ctypes.Structure):
     _fields_ = [
         ("log_n", ctypes.c_uint32), ("blinding_factors", ctypes.c_uint32),
@@ -306,6 +318,12 @@ def _load():
                                      ctypes.c_int),
         "pm_eval_polynomial": ([_vp, ctypes.c_int, _u64p, ctypes.c_size_t, _u64p, _u64p], ctypes.c_int),
         "pm_kate_division": ([_vp, ctypes.c_int, _u64p, ctypes.c_size_t, _u64p, _u64p], ctypes.c_int),
+        "pm_batch_invert_device": ([_vp, ctypes.c_int, _vp, ctypes.c_size_t], ctypes.c_int),
+        "pm_batch_invert": ([_vp, ctypes.c_int, _u64p, ctypes.c_size_t], ctypes.c_int),
+        "pm_grand_product_device": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_size_t, ctypes.c_size_t,
+                                     ctypes.POINTER(PmGpFactor), _u32p, ctypes.POINTER(PmGpFactor), _u32p,
+                                     ctypes.c_size_t, _u64p, _u64p, ctypes.c_size_t, ctypes.c_uint32, _vp, _u64p],
+                                    ctypes.c_int),
         "pm_vk_transcript_repr": ([ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, _u64p], ctypes.c_int),
         "pm_transcript_batch": ([_vp, ctypes.c_int, ctypes.POINTER(PmProofShape), ctypes.c_size_t, _u64p, _u64p,
                                  _u64p, _u64p, _u32p], ctypes.c_int),
@@ -981,6 +999,85 @@ class Context:
         out = np.zeros((max(n, 1) - 1, 4), dtype=np.uint64)
         _check(lib().pm_kate_division(self.h, curve, _p(a), n, _p(zz), _p(out) if n > 1 else None))
         return out
+
+    # ---- grand products (pm_batch_invert* / pm_grand_product_device)
+    def batch_invert_device(self, curve, d_data, n):
+        """pm_batch_invert_device: the n Montgomery scalars at d_data are
+        replaced by their inverses, zeros staying zero."""
+        if n < 0:
+            raise ValueError("negative length")
+        _check(lib().pm_batch_invert_device(self.h, curve, _vp(d_data), n))
+
+    def batch_invert(self, curve, values):
+        """pm_batch_invert (ff::BatchInvert): values (n, 4) u64 Montgomery ->
+        a new (n, 4) array.  Two PCIe crossings: parity, not speed."""
+        a = _as_u64(values, 4).copy()
+        _check(lib().pm_batch_invert(self.h, curve, _p(a), a.shape[0]))
+        return a
+
+    @staticmethod
+    def _gp_factors(lists, C, have_omega):
+        """lists: per set a sequence of factors (x, y, b, g): x a column index
+        or None, y a column index, GP_OMEGA or None, b / g (4,) u64 Montgomery
+        or None for zero -> (PmGpFactor array, offsets (S + 1,) u32)."""
+        flat = [f for fs in lists for f in fs]
+        arr = (PmGpFactor * max(1, len(flat)))()
+        for k, f in enumerate(flat):
+            if len(f) != 4:
+                raise ValueError("a factor is (x, y, b, g)")
+            x, y, b, g = f
+            for name, v, allowed in (("x", x, (None,)), ("y", y, (None, GP_OMEGA))):
+                if v not in allowed and not 0 <= int(v) < C:
+                    raise ValueError(f"factor {name} index {v} out of range (C = {C})")
+            if y == GP_OMEGA and not have_omega:
+                raise ValueError("a factor names GP_OMEGA and omega is None")
+            arr[k].x = GP_NONE if x is None else int(x)
+            arr[k].y = GP_NONE if y is None else int(y)
+            for dst, v in ((arr[k].b, b), (arr[k].g, g)):
+                w = np.zeros(4, dtype=np.uint64) if v is None else np.ascontiguousarray(v, dtype=np.uint64).reshape(-1)
+                if w.shape[0] != 4:
+                    raise ValueError("b and g are one scalar each (4 x u64)")
+                for i in range(4):
+                    dst[i] = int(w[i])
+        offs = np.zeros(len(lists) + 1, dtype=np.uint32)
+        for j, fs in enumerate(lists):
+            if len(fs) > GP_MAX_FACTORS:
+                raise ValueError(f"more than {GP_MAX_FACTORS} factors in a list")
+            offs[j + 1] = offs[j] + len(fs)
+        return arr, offs
+
+    def grand_product_device(self, cid, col_ptrs, n, sets, omega, start, active, out_ptr, chain=False,
+                             want_last=True):
+        """pm_grand_product_device.  col_ptrs: device pointers of the C
+        columns (n Montgomery scalars each); sets: one (numerators,
+        denominators) pair of factor lists per set, a factor being
+        (x, y, b, g) as in _gp_factors; omega (4,) or None; start (4,);
+        out_ptr: S rows of n scalars on the device, rows [0, active) of each
+        are written.  Returns `last` as an (S, 4) array (None with
+        want_last=False)."""
+        sets = [(list(nu), list(de)) for nu, de in sets]
+        S = len(sets)
+        if S == 0:
+            raise ValueError("no set")
+        if not 1 <= active <= n:
+            raise ValueError("active out of range (1 <= active <= n)")
+        st = np.ascontiguousarray(start, dtype=np.uint64).reshape(-1)
+        if st.shape[0] != 4:
+            raise ValueError("start must be one scalar (4 x u64)")
+        w = None
+        if omega is not None:
+            w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(-1)
+            if w.shape[0] != 4:
+                raise ValueError("omega must be one scalar (4 x u64)")
+        ptrs, C = self._poly_ptrs(col_ptrs)
+        num, num_off = self._gp_factors([s[0] for s in sets], C, w is not None)
+        den, den_off = self._gp_factors([s[1] for s in sets], C, w is not None)
+        last = np.zeros((S, 4), dtype=np.uint64) if want_last else None
+        _check(lib().pm_grand_product_device(self.h, cid, ptrs, C, n, num, num_off.ctypes.data_as(_u32p), den,
+                                             den_off.ctypes.data_as(_u32p), S, None if w is None else _p(w), _p(st),
+                                             active, GP_CHAIN if chain else 0, _vp(out_ptr),
+                                             _p(last) if want_last else None))
+        return last
 
     def selftest_field(self, curve, seed, n):
         m = ctypes.c_uint64(0)

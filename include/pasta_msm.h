@@ -536,6 +536,79 @@ int pm_eval_polynomial(pm_ctx* ctx, int curve, const uint64_t* coeffs, size_t n,
 int pm_kate_division(pm_ctx* ctx, int curve, const uint64_t* coeffs, size_t n, const uint64_t z[4],
                      uint64_t* out_q);
 
+/* ---- Grand products ------------------------------------------
+ * The running-product polynomials Z of the permutation argument
+ * (plonk/permutation/prover.rs::commit [3P]) and of every lookup
+ * (plonk/lookup/prover.rs::commit_product [3P]), and ff::BatchInvert [3P]:
+ * the step of create_proof between "columns on the device" and the commit to
+ * Z in Lagrange form (pm_msm_fixed_device).  Exact arithmetic over the scalar
+ * field of `curve`; every scalar is 4 x u64 Montgomery and canonical, in and
+ * out, like pm_fft_device's elements.
+ *
+ * pm_batch_invert_device: a[i] <- a[i]^-1 for the n values at d_data, in
+ *   place; a zero stays zero (BatchInvert's behaviour).
+ * pm_batch_invert: the host-pointer form (copy in, invert, copy out): parity,
+ *   not speed.
+ * pm_grand_product_device: S sets over the same n rows.  A factor is one
+ *   linear term per row,
+ *       f[i] = x[i] + b * y[i] + g
+ *   x: a column index < C, or PM_GP_NONE (contributes 0); y: a column index,
+ *   PM_GP_OMEGA (the implicit column omega^i), or PM_GP_NONE (b is ignored);
+ *   b, g: scalars.  Set j has the numerator factors
+ *   num[num_offsets[j] .. num_offsets[j+1]) and the denominator factors
+ *   den[den_offsets[j] .. den_offsets[j+1]) (offsets[0] = 0; a list may be
+ *   empty, its product is 1; at most PM_GP_MAX_FACTORS per list).  With
+ *   N[i] / D[i] the products of the two lists at row i and inv0(0) = 0:
+ *       z[0]   = start_j
+ *       z[i+1] = z[i] * N[i] * inv0(D[i])        0 <= i < active - 1
+ *       last_j = z[active - 1]
+ *   Rows [0, active) of row j of d_out_z (S rows of n scalars) are written;
+ *   rows [active, n) are left exactly as the caller had them (halo2 fills them
+ *   with blinding values).  Rows i >= active - 1 of the columns enter no
+ *   output.  start_j = start, or with PM_GP_CHAIN in flags start_0 = start and
+ *   start_j = last_{j-1} (the permutation argument's last_z across column
+ *   chunks).  out_last (S scalars, may be NULL) receives last_j.
+ *   d_cols is a HOST array of C DEVICE pointers, each to n scalars; factors,
+ *   offsets, omega, start and out_last are host memory.  omega may be NULL
+ *   when no factor names PM_GP_OMEGA.  n need not be a power of two.  The
+ *   output rows must not alias an input column, nor each other.
+ *
+ *   A permutation chunk over the columns c_1..c_m of a chunk starting at
+ *   column chunk_start: denominators {x = c_k, y = sigma_k, b = beta,
+ *   g = gamma}, numerators {x = c_k, y = PM_GP_OMEGA,
+ *   b = beta * delta^(chunk_start + k), g = gamma}, start = 1,
+ *   active = n - blinding_factors, chunks chained.  A lookup: denominators
+ *   {x = A', g = beta}, {x = S', g = gamma}, numerators {x = A, g = beta},
+ *   {x = S, g = gamma} (y = PM_GP_NONE), not chained.
+ *
+ * PM_ERR_ARG: a null context or pointer (d_cols may be NULL when C == 0), an
+ * unknown curve, n == 0, active == 0 or active > n, S == 0, offsets that do
+ * not start at 0 or decrease, a list longer than PM_GP_MAX_FACTORS, a column
+ * index >= C, PM_GP_OMEGA without omega, unknown flag bits (all checked before
+ * the device is touched).  PM_ERR_UNSUPPORTED: n > 2^28, more than 65535 sets
+ * in one call.  Context scratch: 40 n bytes per set.  One field inversion per
+ * set, none per row. */
+#define PM_GP_NONE  0xFFFFFFFFu
+#define PM_GP_OMEGA 0xFFFFFFFEu
+#define PM_GP_CHAIN 1u
+#define PM_GP_MAX_FACTORS 16           /* per list per set */
+
+typedef struct pm_gp_factor {
+  uint32_t x;        /* column index < C, or PM_GP_NONE */
+  uint32_t y;        /* column index < C, PM_GP_OMEGA, or PM_GP_NONE (b ignored) */
+  uint64_t b[4];     /* Montgomery, like every scalar of this ABI */
+  uint64_t g[4];
+} pm_gp_factor;
+
+int pm_batch_invert_device(pm_ctx* ctx, int curve, void* d_data, size_t n);
+int pm_batch_invert(pm_ctx* ctx, int curve, uint64_t* data, size_t n);   /* host pointers: parity form */
+
+int pm_grand_product_device(pm_ctx* ctx, int curve, const void* const* d_cols, size_t C, size_t n,
+                            const pm_gp_factor* num, const uint32_t* num_offsets,   /* S + 1 entries */
+                            const pm_gp_factor* den, const uint32_t* den_offsets,   /* S + 1 entries */
+                            size_t S, const uint64_t omega[4], const uint64_t start[4], size_t active,
+                            uint32_t flags, void* d_out_z /* S rows of n */, uint64_t* out_last /* S x 4, may be null */);
+
 /* ---- Blake2b transcript replay ------------------------------
  * The verifier squeezes theta, beta, gamma, y, x, v, u from a halo2
  * Blake2bWrite/Challenge255 transcript (TranscriptChip,
