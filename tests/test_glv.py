@@ -5,29 +5,15 @@ lattice vectors satisfy a + b lambda = 0 mod r, and the device's decomposition
 (floor with 2^384-scaled g1, g2) gives |k1|, |k2| < 2^128 with
 k = k1 + lambda k2 mod r on random and edge scalars; with Babai rounding (the
 MSM's GLV mode) |k1|, |k2| < 2^127."""
-import os
 import random
-import re
 
 import pytest
 
 import pasta as P
+from msm_short_edge_util import GLV_HDR as HDR  # noqa: F401  (the header the constants come from)
+from msm_short_edge_util import parse_glv as _parse
 
-HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "halo2-aggregation_amd", "csrc",
-                   "glv.hpp")
 CURVES = {"PallasCurve": P.PALLAS, "VestaCurve": P.VESTA, "Bn254Curve": P.BN254}
-
-
-def _parse():
-    txt = open(HDR).read()
-    out = {}
-    for m in re.finditer(r"template <> struct Glv<(\w+)> \{(.*?)\n\};", txt, re.S):
-        d = {}
-        for a in re.finditer(r"static constexpr uint32_t (\w+)\[\d+\] = \{([^}]*)\}", m.group(2)):
-            limbs = [int(x.strip().rstrip("u"), 16) for x in a.group(2).split(",")]
-            d[a.group(1)] = sum(v << (32 * i) for i, v in enumerate(limbs))
-        out[m.group(1)] = d
-    return out
 
 
 @pytest.mark.parametrize("name", list(CURVES))

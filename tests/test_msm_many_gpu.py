@@ -9,7 +9,10 @@ best_multiexp (oracle/msm_ref.c) on the same scalars and base window:
 * edge inputs: n_i = 0, identity bases, zero scalars, r - 1, canonical
   scalars >= r, the same base in every MSM, P and -P in one MSM
 * the device-scalar entry, the table's growth (a later call reaching further
-  into the set rebuilds it with a narrower window when the prefix needs it)
+  into the set rebuilds it for a longer prefix)
+Every prefix here has at most 4096 bases, so the table's window is always
+c = 8; the narrower windows (c = 7, 6, 5, 4), the rebuild with a narrower
+window and the fallback past 131072 bases are in test_msm_short_edges_gpu.py.
 """
 import numpy as np
 import pytest
