@@ -908,6 +908,7 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
 #include "msm_many.hpp"
 #include "poly_engine.hpp"
 #include "gp_engine.hpp"
+#include "domain_engine.hpp"
 
 // Explicit instantiations are visible to both compilation passes, so the
 // device pass instantiates every kernel the host driver launches; the op
@@ -925,7 +926,8 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
                          &bases_to29_impl<Cv>, &msm_resident_batch_impl<Cv>, &proofs_device_impl<Cv>,    \
                          &msm_start_impl<Cv>, &msm_finish_impl<Cv>, &msm_small_impl<Cv>,         \
                          &many_table_impl<Cv>, &msm_many_impl<Cv>, &points_sum_impl<typename Cv::Base>, \
-                         &poly_eval_impl<Cv>, &poly_witness_impl<Cv>, &grand_product_impl<Cv>};
+                         &poly_eval_impl<Cv>, &poly_witness_impl<Cv>, &grand_product_impl<Cv>,          \
+                         &domain_tables_impl<Cv>, &domain_run_impl<Cv>};
 #endif
 #define PM_DEFINE_CURVE_OPS(Cv, name)                                                          \
   namespace pm {                                                                               \
@@ -960,5 +962,8 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
   template int grand_product_impl<Cv>(Ctx*, int, const void* const*, size_t, size_t, const pm_gp_factor*, const uint32_t*, \
                                       const pm_gp_factor*, const uint32_t*, size_t, const uint64_t*, const uint64_t*, \
                                       size_t, uint32_t, void*, uint64_t*);                       \
+  template int domain_tables_impl<Cv>(uint32_t, uint32_t, const uint64_t*, const uint64_t*, pm_domain*,        \
+                                      std::vector<uint64_t>*);                                   \
+  template int domain_run_impl<Cv>(Ctx*, const DomJob*);                                         \
   PM_OPS_TABLE(Cv, name)                                                                       \
   }

@@ -1457,6 +1457,170 @@ int pm_batch_invert(pm_ctx* ctx, int curve, uint64_t* data, size_t n) {
   return PM_OK;
 }
 
+// ------------------------------------------------- extended-domain conversions (§8f-7)
+int pm_domain_create(pm_ctx* ctx, int curve, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
+                     const uint64_t zeta[4], pm_domain** out) {
+  if (!ctx || !extended_omega || !zeta || !out) return set_error(PM_ERR_ARG, "null argument");
+  *out = nullptr;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return set_error(PM_ERR_ARG, "unknown curve id");
+  if (extended_k < k) return set_error(PM_ERR_ARG, "extended_k below k");
+  if (extended_k > pm::kNttMaxLog) return set_error(PM_ERR_UNSUPPORTED, "extended domain longer than 2^28");
+  if (extended_k - k > pm::kDomMaxE) return set_error(PM_ERR_UNSUPPORTED, "extended_k - k above 8");
+  std::unique_ptr<pm_domain> d(new pm_domain{curve, ctx->device, k, extended_k, {}, {}, {}, nullptr});
+  std::vector<uint64_t> tab;
+  int rc = ops->domain_tables(k, extended_k, extended_omega, zeta, d.get(), &tab);  // host only
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if ((rc = ctx->begin_call())) return rc;
+  HIP_TRY(hipMalloc(&d->d_tab, tab.size() * 8));
+  if (hipMemcpy(d->d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d->d_tab);
+    return set_error(PM_ERR_HIP, "upload of the domain tables failed");
+  }
+  *out = d.release();
+  return PM_OK;
+}
+
+int pm_domain_info(const pm_domain* d, uint32_t* k, uint32_t* extended_k, uint64_t omega[4], uint32_t* t_len) {
+  if (!d) return set_error(PM_ERR_ARG, "null argument");
+  if (k) *k = d->k;
+  if (extended_k) *extended_k = d->ext_k;
+  if (omega) std::memcpy(omega, d->omega, 32);
+  if (t_len) *t_len = 1u << (d->ext_k - d->k);
+  return PM_OK;
+}
+
+int pm_domain_release(pm_domain* d) {
+  if (!d) return PM_OK;
+  if (d->d_tab) {
+    (void)hipSetDevice(d->device);
+    (void)hipFree(d->d_tab);
+  }
+  delete d;
+  return PM_OK;
+}
+
+namespace {
+// shared checks of the column entries; everything here runs before the device is touched
+int domain_check(pm_ctx* ctx, const pm_domain* d, const void* const* d_in, bool has_in, void* const* d_out, size_t C) {
+  if (!ctx || !d || (C && (!d_out || (has_in && !d_in)))) return set_error(PM_ERR_ARG, "null argument");
+  if (d->device != ctx->device) return set_error(PM_ERR_ARG, "the domain lives on another device");
+  for (size_t c = 0; c < C; c++)
+    if (!d_out[c] || (has_in && !d_in[c])) return set_error(PM_ERR_ARG, "null column pointer");
+  if (C > pm::kPolyMaxGridY) return set_error(PM_ERR_UNSUPPORTED, "more than 65535 columns in one call");
+  return PM_OK;
+}
+
+// with the context's mutex held
+int domain_run_locked(pm_ctx* ctx, const pm_domain* d, int op, const void* const* d_in, void* const* d_out, size_t C,
+                      size_t keep, uint32_t flags) {
+  int rc = ctx->begin_call();
+  if (rc) return rc;
+  pm::DomJob job{};
+  job.op = op;
+  job.curve = d->curve;
+  job.logn = d->ext_k;
+  job.omega = op == pm::kDomOpToCoeff ? d->omega_e_inv : d->omega_e;
+  job.dom = d;
+  job.d_in = d_in;
+  job.d_out = d_out;
+  job.C = C;
+  job.keep = keep;
+  job.flags = flags;
+  return curve_ops(d->curve)->domain_run(ctx, &job);
+}
+
+int ext_to_coeff_check(const pm_domain* d, size_t keep, uint32_t flags) {
+  if (keep == 0 || keep > ((size_t)1 << d->ext_k)) return set_error(PM_ERR_ARG, "keep out of range (1 <= keep <= N)");
+  if (flags & ~(uint32_t)PM_EXT_DIVIDE_VANISHING) return set_error(PM_ERR_ARG, "unknown flag bits");
+  return PM_OK;
+}
+}  // namespace
+
+int pm_coeff_to_extended_device(pm_ctx* ctx, const pm_domain* d, const void* const* d_in, void* const* d_out,
+                                size_t C) {
+  int rc = domain_check(ctx, d, d_in, true, d_out, C);
+  if (rc || C == 0) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return domain_run_locked(ctx, d, pm::kDomOpToExt, d_in, d_out, C, 0, 0);
+}
+
+int pm_extended_to_coeff_device(pm_ctx* ctx, const pm_domain* d, const void* const* d_in, void* const* d_out, size_t C,
+                                size_t keep, uint32_t flags) {
+  int rc = domain_check(ctx, d, d_in, true, d_out, C);
+  if (rc || (rc = ext_to_coeff_check(d, keep, flags)) || C == 0) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return domain_run_locked(ctx, d, pm::kDomOpToCoeff, d_in, d_out, C, keep, flags);
+}
+
+int pm_divide_by_vanishing_device(pm_ctx* ctx, const pm_domain* d, void* const* d_data, size_t C) {
+  int rc = domain_check(ctx, d, nullptr, false, d_data, C);
+  if (rc || C == 0) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return domain_run_locked(ctx, d, pm::kDomOpDivide, nullptr, d_data, C, 0, 0);
+}
+
+int pm_fft_batch_device(pm_ctx* ctx, int curve, void* const* d_data, size_t C, uint32_t log_n, const uint64_t omega[4],
+                        const uint64_t* scale) {
+  if (!ctx || !omega || (C && !d_data)) return set_error(PM_ERR_ARG, "null argument");
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return set_error(PM_ERR_ARG, "unknown curve id");
+  for (size_t c = 0; c < C; c++)
+    if (!d_data[c]) return set_error(PM_ERR_ARG, "null column pointer");
+  if (log_n > pm::kNttMaxLog) return set_error(PM_ERR_UNSUPPORTED, "NTT longer than 2^28");
+  if (C > pm::kPolyMaxGridY) return set_error(PM_ERR_UNSUPPORTED, "more than 65535 columns in one call");
+  if (C == 0) return PM_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = ctx->begin_call();
+  if (rc) return rc;
+  pm::DomJob job{};
+  job.op = pm::kDomOpFft;
+  job.curve = curve;
+  job.logn = log_n;
+  job.omega = omega;
+  job.scale = scale;
+  job.d_out = d_data;
+  job.C = C;
+  return ops->domain_run(ctx, &job);
+}
+
+int pm_coeff_to_extended(pm_ctx* ctx, const pm_domain* d, const uint64_t* coeffs, uint64_t* out) {
+  if (!ctx || !d || !coeffs || !out) return set_error(PM_ERR_ARG, "null argument");
+  if (d->device != ctx->device) return set_error(PM_ERR_ARG, "the domain lives on another device");
+  const size_t n = (size_t)1 << d->k, N = (size_t)1 << d->ext_k;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = ctx->begin_call();
+  if (rc) return rc;
+  if ((rc = ctx->in_scalars.ensure(N * 32))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->in_scalars.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  const void* in = ctx->in_scalars.p;  // the input is the prefix of its own output buffer
+  void* buf = ctx->in_scalars.p;
+  if ((rc = domain_run_locked(ctx, d, pm::kDomOpToExt, &in, &buf, 1, 0, 0))) return rc;
+  HIP_TRY(hipMemcpyAsync(out, ctx->in_scalars.p, N * 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
+int pm_extended_to_coeff(pm_ctx* ctx, const pm_domain* d, const uint64_t* evals, size_t keep, uint32_t flags,
+                         uint64_t* out) {
+  if (!ctx || !d || !evals || !out) return set_error(PM_ERR_ARG, "null argument");
+  if (d->device != ctx->device) return set_error(PM_ERR_ARG, "the domain lives on another device");
+  int rc = ext_to_coeff_check(d, keep, flags);
+  if (rc) return rc;
+  const size_t N = (size_t)1 << d->ext_k;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if ((rc = ctx->begin_call())) return rc;
+  if ((rc = ctx->in_scalars.ensure(N * 32))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->in_scalars.p, evals, N * 32, hipMemcpyHostToDevice, ctx->stream));
+  const void* in = ctx->in_scalars.p;
+  void* buf = ctx->in_scalars.p;
+  if ((rc = domain_run_locked(ctx, d, pm::kDomOpToCoeff, &in, &buf, 1, keep, flags))) return rc;
+  HIP_TRY(hipMemcpyAsync(out, ctx->in_scalars.p, keep * 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
 // ------------------------------------------------- fixed-base MSM (§8f-3)
 static int fixed_create(pm_ctx* ctx, int curve, const void* bases, bool host, size_t n, int c, int rows,
                         pm_fixed_bases** out) {

@@ -84,26 +84,18 @@ constexpr int kNttMaxLogC = 2;
 // profiles/r03/ntt_f29/threads_ab3.jsonl)
 constexpr unsigned kNttThreads2 = 512, kNttThreads3 = 256;
 
-template <class Cv>
-int ntt_device_impl(Ctx* ctx, int curve, void* d_data, uint32_t logn, const uint64_t omega[4],
-                    const uint64_t* scale) {
-  using Fs = typename Cv::Scalar;
-  if (logn > kNttMaxLog) return set_error(PM_ERR_UNSUPPORTED, "NTT longer than 2^28");
-  if (logn == 0) {
-    if (scale) {  // a_0 *= scale
-      // a one-element transform is the identity; apply the scale on the host
-      uint64_t v[4];
-      HIP_TRY(hipMemcpyAsync(v, d_data, 32, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      const Fe<Fs> r = fe_mul<Fs>(fe_from_u64<Fs>(v), fe_from_u64<Fs>(scale));
-      for (int k = 0; k < 4; k++) v[k] = (uint64_t)r.l[2 * k] | ((uint64_t)r.l[2 * k + 1] << 32);
-      HIP_TRY(hipMemcpyAsync(d_data, v, 32, hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    return PM_OK;
-  }
+// Factorisation, launch shapes' inputs and twiddle segments of one transform
+// length: [sub-transform segments | lo | hi] (ntt_kernels.hpp), looked up in
+// the context's cache and filled on a miss.  Shared by pm_fft* and the
+// extended-domain conversions (domain_engine.hpp).
+struct NttPlan {
+  int passes, log1, loga, logb, s2;
+  const uint32_t *twA, *twM, *twB, *twLo, *twHi;
+};
+
+template <class Fs>
+int ntt_plan(Ctx* ctx, int curve, uint32_t logn, const uint64_t omega[4], NttPlan* pl) {
   const hipStream_t st = ctx->stream;
-  const size_t n = (size_t)1 << logn;
   // factorisation and twiddle segments: [sub-transform segments | lo | hi]
   const int passes = logn <= (uint32_t)kNttOnePassLog ? 1 : ntt_passes(ctx, logn);
   int log1 = (int)logn, loga = 0, logb = 0;
@@ -144,8 +136,36 @@ int ntt_device_impl(Ctx* ctx, int curve, void* d_data, uint32_t logn, const uint
     PM_LAUNCH(ctx, "ntt_twiddles", (k_ntt_twiddles<Fs><<<(tot + 255) / 256, 256, 0, st>>>(
                                        fearg_from_u64<Fs>(omega), sg, (uint32_t*)tw)));
   }
-  const uint32_t *twA = tw + 8ull * sg.off[sA], *twM = tw + 8ull * sg.off[sM], *twB = tw + 8ull * sg.off[sB];
-  const uint32_t *twLo = tw + 8ull * sg.off[sLo], *twHi = tw + 8ull * sg.off[sHi];
+  *pl = NttPlan{passes, log1, loga, logb, s2, tw + 8ull * sg.off[sA], tw + 8ull * sg.off[sM], tw + 8ull * sg.off[sB],
+                tw + 8ull * sg.off[sLo], tw + 8ull * sg.off[sHi]};
+  return PM_OK;
+}
+
+template <class Cv>
+int ntt_device_impl(Ctx* ctx, int curve, void* d_data, uint32_t logn, const uint64_t omega[4],
+                    const uint64_t* scale) {
+  using Fs = typename Cv::Scalar;
+  if (logn > kNttMaxLog) return set_error(PM_ERR_UNSUPPORTED, "NTT longer than 2^28");
+  if (logn == 0) {
+    if (scale) {  // a_0 *= scale
+      // a one-element transform is the identity; apply the scale on the host
+      uint64_t v[4];
+      HIP_TRY(hipMemcpyAsync(v, d_data, 32, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      const Fe<Fs> r = fe_mul<Fs>(fe_from_u64<Fs>(v), fe_from_u64<Fs>(scale));
+      for (int k = 0; k < 4; k++) v[k] = (uint64_t)r.l[2 * k] | ((uint64_t)r.l[2 * k + 1] << 32);
+      HIP_TRY(hipMemcpyAsync(d_data, v, 32, hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return PM_OK;
+  }
+  const hipStream_t st = ctx->stream;
+  const size_t n = (size_t)1 << logn;
+  NttPlan pl;
+  int rc = ntt_plan<Fs>(ctx, curve, logn, omega, &pl);
+  if (rc) return rc;
+  const int passes = pl.passes, log1 = pl.log1, loga = pl.loga, logb = pl.logb, s2 = pl.s2;
+  const uint32_t *twA = pl.twA, *twM = pl.twM, *twB = pl.twB, *twLo = pl.twLo, *twHi = pl.twHi;
   const FeArg sc = scale ? fearg_from_u64<Fs>(scale) : FeArg{};
   const unsigned nt2 = kNttThreads2, nt3 = kNttThreads3;
   uint32_t* data = (uint32_t*)d_data;

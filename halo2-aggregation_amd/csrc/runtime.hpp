@@ -173,6 +173,18 @@ struct pm_fixed_bases {
   void* d;
 };
 
+// Extended evaluation domain (pm_domain_create, domain_engine.hpp): the roots
+// as the caller's R = 2^256 Montgomery words, and the device table the
+// kernels read, R = 2^261 canonical packed:
+// [zeta^0..2 | N^-1 zeta^-0..-2 | t_0 .. t_{2^e - 1}].
+struct pm_domain {
+  int curve;
+  int device;
+  uint32_t k, ext_k;
+  uint64_t omega[4], omega_e[4], omega_e_inv[4];
+  void* d_tab;
+};
+
 namespace pm {
 // multiples table of a resident base set (msm_many.hpp): entry (i, w, m) =
 // [m 2^{c w}] P_i, m = 1 .. H = 2^(c-1), w < W, XYZZ R = 2^261 (128 B), for
@@ -208,6 +220,21 @@ constexpr size_t kPolyMaxGridY = 65535;        // sets / pairs per call (grid.y)
 // grand products (gp_engine.hpp): the same limits; flag bit of CurveOps::grand_product
 // for the in-place batch inversion (never part of the C-ABI's flags)
 constexpr uint32_t kGpInvert = 0x80000000u;
+// extended-domain conversions (domain_engine.hpp): one job of CurveOps::domain_run
+enum : int { kDomOpFft = 0, kDomOpToExt = 1, kDomOpToCoeff = 2, kDomOpDivide = 3 };
+constexpr uint32_t kDomDivideVanishing = 1u;  // PM_EXT_DIVIDE_VANISHING
+constexpr uint32_t kDomMaxE = 8;              // extended_k - k
+struct DomJob {
+  int op, curve;
+  uint32_t logn;              // transform length (extended_k of dom, or log_n of the batched NTT)
+  const uint64_t* omega;      // root of the transform
+  const uint64_t* scale;      // kDomOpFft: pm_fft's scale, or null
+  const pm_domain* dom;       // null for kDomOpFft
+  const void* const* d_in;    // host arrays of C device pointers; d_in null: in place on d_out
+  void* const* d_out;
+  size_t C, keep;
+  uint32_t flags;
+};
 struct NttTwiddles {
   int curve = -1;
   uint32_t logn = 0;
@@ -272,6 +299,8 @@ struct pm_ctx {
   pm::Buf poly_job, poly_tab, poly_aux, poly_q;
   // grand products (gp_engine.hpp): the un-carried suffix products, S rows of n (the rest shares the three above)
   pm::Buf gp_rows;
+  // extended-domain conversions (domain_engine.hpp): the call's column pointer tables
+  pm::Buf dom_ptrs;
   // the power table of the last omega a grand product named: one prover calls with one omega, and the
   // table's chain of squarings is pure latency (0.04 ms of a 2^20 call); valid while gp_tab.gen == gp_tab_gen
   pm::Buf gp_tab;
@@ -317,7 +346,7 @@ struct pm_ctx {
   std::vector<pm::Buf*> all_bufs() {
     return {&in_scalars, &in_scalars2, &in_bases, &digits, &sorted, &counts, &offsets, &cursor,
             &bsum,       &buckets,  &head,   &segS,   &segT,   &bits,    &win, &longs, &mid,
-            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1], &poly_job, &poly_tab, &poly_aux, &poly_q, &gp_rows, &gp_tab};
+            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1], &poly_job, &poly_tab, &poly_aux, &poly_q, &gp_rows, &gp_tab, &dom_ptrs};
   }
   ~pm_ctx();
   int begin_call();
@@ -404,6 +433,11 @@ struct CurveOps {
                        const uint32_t* num_off, const pm_gp_factor* den, const uint32_t* den_off, size_t S,
                        const uint64_t* omega, const uint64_t* start, size_t active, uint32_t flags, void* d_out,
                        uint64_t* out_last);
+  // extended-domain conversions (domain_engine.hpp): host-only check of the
+  // roots + the device table's words; one conversion / batched NTT / division
+  int (*domain_tables)(uint32_t k, uint32_t ext_k, const uint64_t* omega_e, const uint64_t* zeta, pm_domain* d,
+                       std::vector<uint64_t>* tab);
+  int (*domain_run)(Ctx* ctx, const DomJob* job);
 };
 extern const CurveOps kPallasOps, kVestaOps, kBn254Ops;
 

@@ -69,6 +69,7 @@ GP_NONE = 0xFFFFFFFF
 GP_OMEGA = 0xFFFFFFFE
 GP_CHAIN = 1
 GP_MAX_FACTORS = 16
+EXT_DIVIDE_VANISHING = 1  # PM_EXT_DIVIDE_VANISHING
 
 
 class PmGpFactor(ctypes.Structure):
@@ -324,6 +325,19 @@ def _load():
                                      ctypes.POINTER(PmGpFactor), _u32p, ctypes.POINTER(PmGpFactor), _u32p,
                                      ctypes.c_size_t, _u64p, _u64p, ctypes.c_size_t, ctypes.c_uint32, _vp, _u64p],
                                     ctypes.c_int),
+        "pm_domain_create": ([_vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p, ctypes.POINTER(_vp)],
+                             ctypes.c_int),
+        "pm_domain_info": ([_vp, _u32p, _u32p, _u64p, _u32p], ctypes.c_int),
+        "pm_domain_release": ([_vp], ctypes.c_int),
+        "pm_coeff_to_extended_device": ([_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_size_t],
+                                        ctypes.c_int),
+        "pm_extended_to_coeff_device": ([_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_size_t,
+                                         ctypes.c_size_t, ctypes.c_uint32], ctypes.c_int),
+        "pm_divide_by_vanishing_device": ([_vp, _vp, ctypes.POINTER(_vp), ctypes.c_size_t], ctypes.c_int),
+        "pm_fft_batch_device": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_size_t, ctypes.c_uint32, _u64p,
+                                 _u64p], ctypes.c_int),
+        "pm_coeff_to_extended": ([_vp, _vp, _u64p, _u64p], ctypes.c_int),
+        "pm_extended_to_coeff": ([_vp, _vp, _u64p, ctypes.c_size_t, ctypes.c_uint32, _u64p], ctypes.c_int),
         "pm_vk_transcript_repr": ([ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, _u64p], ctypes.c_int),
         "pm_transcript_batch": ([_vp, ctypes.c_int, ctypes.POINTER(PmProofShape), ctypes.c_size_t, _u64p, _u64p,
                                  _u64p, _u64p, _u32p], ctypes.c_int),
@@ -556,6 +570,44 @@ class FixedBases:
     def release(self):
         if self.h:
             lib().pm_fixed_bases_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class Domain:
+    """pm_domain: an extended evaluation domain (halo2 EvaluationDomain) of
+    n = 2^k rows and N = 2^extended_k extended rows on the context's device;
+    extended_omega and zeta are (4,) u64 Montgomery scalars."""
+
+    def __init__(self, ctx, curve, k, extended_k, extended_omega, zeta):
+        self.h = None
+        if k < 0 or extended_k < k:
+            raise ValueError("0 <= k <= extended_k")
+        we = np.ascontiguousarray(extended_omega, dtype=np.uint64).reshape(-1)
+        z = np.ascontiguousarray(zeta, dtype=np.uint64).reshape(-1)
+        if we.shape[0] != 4 or z.shape[0] != 4:
+            raise ValueError("extended_omega and zeta are one scalar each (4 x u64)")
+        h = _vp()
+        _check(lib().pm_domain_create(ctx.h, curve, k, extended_k, _p(we), _p(z), ctypes.byref(h)))
+        self.h = h
+        self.curve, self.k, self.extended_k = curve, k, extended_k
+        self.n, self.N = 1 << k, 1 << extended_k
+
+    def info(self):
+        """(k, extended_k, omega (4,) u64 Montgomery, len(t_evaluations))"""
+        k, ek, tl = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        w = np.zeros(4, dtype=np.uint64)
+        _check(lib().pm_domain_info(self.h, ctypes.byref(k), ctypes.byref(ek), _p(w), ctypes.byref(tl)))
+        return k.value, ek.value, w, tl.value
+
+    def release(self):
+        if self.h is not None:
+            lib().pm_domain_release(self.h)
             self.h = None
 
     def __del__(self):
@@ -1078,6 +1130,78 @@ class Context:
                                              active, GP_CHAIN if chain else 0, _vp(out_ptr),
                                              _p(last) if want_last else None))
         return last
+
+    # ---- extended-domain conversions (pm_coeff_to_extended* / pm_extended_to_coeff* /
+    # pm_divide_by_vanishing_device / pm_fft_batch_device): d_in / d_out / d_data are
+    # sequences of device pointers, one per column
+    @staticmethod
+    def _col_ptrs(*lists):
+        ptrs = [[int(p) for p in l] for l in lists]
+        if any(len(l) != len(ptrs[0]) for l in ptrs):
+            raise ValueError("one output pointer per input pointer")
+        if any(p == 0 for l in ptrs for p in l):
+            raise ValueError("null column pointer")
+        return [(_vp * max(1, len(l)))(*l) for l in ptrs], len(ptrs[0])
+
+    def domain(self, curve, k, extended_k, extended_omega, zeta):
+        return Domain(self, curve, k, extended_k, extended_omega, zeta)
+
+    def coeff_to_extended_device(self, dom: Domain, d_in, d_out):
+        """pm_coeff_to_extended_device: column c reads dom.n scalars at d_in[c]
+        and writes dom.N at d_out[c] (which may equal d_in[c])."""
+        (pi, po), C = self._col_ptrs(d_in, d_out)
+        _check(lib().pm_coeff_to_extended_device(self.h, dom.h, pi, po, C))
+
+    def extended_to_coeff_device(self, dom: Domain, d_in, d_out, keep, divide_vanishing=False):
+        """pm_extended_to_coeff_device: column c reads dom.N scalars at d_in[c]
+        and writes `keep` at d_out[c] (which may equal d_in[c]);
+        divide_vanishing: PM_EXT_DIVIDE_VANISHING."""
+        (pi, po), C = self._col_ptrs(d_in, d_out)
+        if not 1 <= keep <= dom.N:
+            raise ValueError("keep out of range (1 <= keep <= N)")
+        _check(lib().pm_extended_to_coeff_device(self.h, dom.h, pi, po, C, keep,
+                                                 EXT_DIVIDE_VANISHING if divide_vanishing else 0))
+
+    def divide_by_vanishing_device(self, dom: Domain, d_data):
+        """pm_divide_by_vanishing_device: dom.N scalars per column, in place."""
+        (pd,), C = self._col_ptrs(d_data)
+        _check(lib().pm_divide_by_vanishing_device(self.h, dom.h, pd, C))
+
+    def fft_batch_device(self, curve, d_data, log_n, omega, scale=None):
+        """pm_fft_batch_device: fft_device on every column of d_data, one
+        synchronisation."""
+        (pd,), C = self._col_ptrs(d_data)
+        w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.uint64).reshape(-1)
+        if w.shape[0] != 4 or (sc is not None and sc.shape[0] != 4):
+            raise ValueError("omega and scale are one scalar each (4 x u64)")
+        if not 0 <= log_n <= 28:
+            raise ValueError("log_n out of range (0 .. 28)")
+        _check(lib().pm_fft_batch_device(self.h, curve, pd, C, log_n, _p(w), None if sc is None else _p(sc)))
+
+    def coeff_to_extended(self, dom: Domain, coeffs):
+        """pm_coeff_to_extended: coeffs (n, 4) u64 Montgomery -> (N, 4).  Two
+        PCIe crossings: parity, not speed."""
+        a = _as_u64(coeffs, 4)
+        if a.shape[0] != dom.n:
+            raise ValueError("coeffs must hold n = 2^k scalars")
+        out = np.zeros((dom.N, 4), dtype=np.uint64)
+        _check(lib().pm_coeff_to_extended(self.h, dom.h, _p(a), _p(out)))
+        return out
+
+    def extended_to_coeff(self, dom: Domain, evals, keep=None, divide_vanishing=False):
+        """pm_extended_to_coeff: evals (N, 4) u64 Montgomery -> (keep, 4)
+        (keep defaults to N)."""
+        a = _as_u64(evals, 4)
+        if a.shape[0] != dom.N:
+            raise ValueError("evals must hold N = 2^extended_k scalars")
+        keep = dom.N if keep is None else keep
+        if not 1 <= keep <= dom.N:
+            raise ValueError("keep out of range (1 <= keep <= N)")
+        out = np.zeros((keep, 4), dtype=np.uint64)
+        _check(lib().pm_extended_to_coeff(self.h, dom.h, _p(a), keep,
+                                          EXT_DIVIDE_VANISHING if divide_vanishing else 0, _p(out)))
+        return out
 
     def selftest_field(self, curve, seed, n):
         m = ctypes.c_uint64(0)

@@ -609,6 +609,84 @@ int pm_grand_product_device(pm_ctx* ctx, int curve, const void* const* d_cols, s
                             size_t S, const uint64_t omega[4], const uint64_t start[4], size_t active,
                             uint32_t flags, void* d_out_z /* S rows of n */, uint64_t* out_last /* S x 4, may be null */);
 
+/* ---- Extended-domain conversions -----------------------------
+ * halo2 `EvaluationDomain::{coeff_to_extended, extended_to_coeff,
+ * divide_by_vanishing_poly}` [3P poly/domain.rs]: the transforms around the
+ * quotient polynomial h(X) in create_proof, batched over columns and fused
+ * into the NTT passes of pm_fft_device (no pass over memory of their own).
+ * With r the scalar field of `curve`, n = 2^k, N = 2^extended_k,
+ * e = extended_k - k, omega_e = extended_omega a primitive N-th root of unity
+ * and zeta a primitive cube root of unity (halo2's g_coset = ZETA,
+ * g_coset_inv = zeta^2):
+ *   coeff_to_extended(a), |a| = n:  out[j] = a(zeta omega_e^j), 0 <= j < N
+ *     (a[i] zeta^(i mod 3), zero-extended to N, best_fft with omega_e);
+ *   divide_by_vanishing_poly(h), |h| = N:  h[j] <- h[j] t[j mod 2^e],
+ *     t[i] = (zeta^n (omega_e^n)^i - 1)^-1, the inverse of X^n - 1 on the coset;
+ *   extended_to_coeff(h), |h| = N:  best_fft with omega_e^-1, times N^-1,
+ *     times zeta^-(i mod 3), truncated to `keep` coefficients (halo2:
+ *     keep = n * quotient_poly_degree, extended_k the smallest with N >= keep).
+ * Exact field arithmetic; every scalar is 4 x u64 Montgomery and canonical,
+ * in and out, like pm_fft's elements.
+ *
+ * pm_domain_create computes on the host, and checks before the device is
+ *   touched: omega = omega_e^(2^e), omega_e^-1, the three output scales
+ *   N^-1 zeta^-j and the 2^e entries of t; then uploads the tables the kernels
+ *   read ((6 + 2^e) x 32 B).  A domain belongs to the context's device and
+ *   may be used by any context of that device; release it with
+ *   pm_domain_release.  pm_domain_info returns k, extended_k, omega and 2^e
+ *   (any output pointer may be NULL).
+ *
+ * d_in / d_out / d_data are HOST arrays of C DEVICE pointers, one per column.
+ * C == 0 succeeds and writes nothing.
+ * pm_coeff_to_extended_device: column c reads n scalars at d_in[c] and
+ *   writes N at d_out[c].  d_out[c] may equal d_in[c] (the input is the
+ *   prefix of its own output buffer); otherwise it must not overlap d_in[c].
+ *   No column's buffer may overlap another column's.
+ * pm_extended_to_coeff_device: column c reads N scalars at d_in[c] and writes
+ *   `keep` at d_out[c], 1 <= keep <= N; nothing beyond d_out[c][keep) is
+ *   written.  d_out[c] may equal d_in[c], and elements [keep, N) of the
+ *   buffer are then unspecified; otherwise d_out[c] must not overlap d_in[c]
+ *   and the input is left unchanged.  With PM_EXT_DIVIDE_VANISHING in flags
+ *   the input is divided by the vanishing polynomial on the way in: the same
+ *   result as pm_divide_by_vanishing_device followed by the plain call.  No
+ *   column's buffer may overlap another column's.
+ * pm_divide_by_vanishing_device: N scalars per column, in place.
+ * pm_fft_batch_device: pm_fft_device on each of the C columns at d_data, in
+ *   place, with one synchronisation: the same results as C calls.
+ * pm_coeff_to_extended / pm_extended_to_coeff: host-pointer forms of one
+ *   column (copy in, convert, copy out; out holds N resp. keep scalars).
+ *   Two PCIe crossings: parity, not speed.
+ *
+ * PM_ERR_ARG: a null context, domain or pointer (a column array may be NULL
+ * when C == 0), an unknown curve, extended_k < k, zeta = 1 or zeta^3 != 1,
+ * omega_e not of exact order N (omega_e^(N/2) != -1; omega_e != 1 when
+ * N = 1), a domain of another device, keep == 0 or keep > N, unknown flag
+ * bits.  PM_ERR_UNSUPPORTED: extended_k > 28, e > 8, more than 65535 columns
+ * in one call.  k == 0 and e == 0 are legal.
+ * Context scratch: the transforms above 2^7 take N x 32 B per column in
+ * flight (twice that above 2^22, the three-pass form), shared with pm_fft's;
+ * the columns of a call run in groups whose scratch fits 256 MiB per pass
+ * buffer, at least one column at a time. */
+typedef struct pm_domain pm_domain;
+int pm_domain_create(pm_ctx* ctx, int curve, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
+                     const uint64_t zeta[4], pm_domain** out);
+int pm_domain_info(const pm_domain* d, uint32_t* k, uint32_t* extended_k, uint64_t omega[4], uint32_t* t_len);
+int pm_domain_release(pm_domain* d);
+
+#define PM_EXT_DIVIDE_VANISHING 1u
+int pm_coeff_to_extended_device(pm_ctx* ctx, const pm_domain* d, const void* const* d_in /* C x n */,
+                                void* const* d_out /* C x N */, size_t C);
+int pm_extended_to_coeff_device(pm_ctx* ctx, const pm_domain* d, const void* const* d_in /* C x N */,
+                                void* const* d_out /* C x keep */, size_t C, size_t keep, uint32_t flags);
+int pm_divide_by_vanishing_device(pm_ctx* ctx, const pm_domain* d, void* const* d_data /* C x N, in place */,
+                                  size_t C);
+int pm_fft_batch_device(pm_ctx* ctx, int curve, void* const* d_data, size_t C, uint32_t log_n,
+                        const uint64_t omega[4], const uint64_t* scale);
+/* host pointers, one column: parity forms */
+int pm_coeff_to_extended(pm_ctx* ctx, const pm_domain* d, const uint64_t* coeffs, uint64_t* out);
+int pm_extended_to_coeff(pm_ctx* ctx, const pm_domain* d, const uint64_t* evals, size_t keep, uint32_t flags,
+                         uint64_t* out);
+
 /* ---- Blake2b transcript replay ------------------------------
  * The verifier squeezes theta, beta, gamma, y, x, v, u from a halo2
  * Blake2bWrite/Challenge255 transcript (TranscriptChip,
