@@ -241,11 +241,15 @@ __device__ __forceinline__ void acc_lagrange_q(const AccumHdr& h, const LdsRows&
     if (q == 0) {
       if (s < h.log_n) xn = r;
     } else if (valid) {
+      // stores only by a quad that owns a proof: a quad beyond the block's
+      // proofs (it repeats proof b0's chain) has no column of its own, and
+      // with fewer than 15 proofs per block (np + 1 < 16 columns) its column
+      // index p aliases row + 1 of proof p - np - 1
       if (kind == 0) {
         den = r;
-        put29(ic, r);
+        if (own) put29(ic, r);
       } else if (kind == 1) {
-        put29(K + ic, r);
+        if (own) put29(K + ic, r);
       } else {
         pre = r;
       }

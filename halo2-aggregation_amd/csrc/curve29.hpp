@@ -267,7 +267,9 @@ __device__ __forceinline__ Xyzz29<F> xyzz29_add(const Xyzz29<F>& p, const Xyzz29
   const F29<F> R = f29_norm<F>(f29_sub<F>(S2, S1, K::K6));
   if (f29_is_zero_mod<F>(P)) {
     // p == q: the doubling takes X, Y < 4p (an input may be a k_acc_powers_s
-    // table point, X, Y < 9.4p: reduce first; never taken in practice)
+    // table point, X, Y < 9.4p: reduce first).  Taken when two terms of an
+    // output are the same point, e.g. k_acc_sum with one or two lanes per
+    // output on equal products (tests/test_accum_edges_gpu.py plants them)
     if (f29_is_zero_mod<F>(R))
       return xyzz29_dbl<F>(Xyzz29<F>{f29_reduce3<F>(p.X), f29_reduce3<F>(p.Y), p.ZZ, p.ZZZ});
     return xyzz29_inf<F>();

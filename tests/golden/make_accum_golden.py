@@ -39,7 +39,11 @@ CASES = [
 
 def edit_edge(C, sh, proofs):
     """Identity commitments / witnesses, zero and equal evals, repeated points:
-    exercises the identity and P == Q branches of the group law."""
+    exercises the identity inputs and zero scalars.  It does NOT reach the
+    P == Q or P == -Q branches of the group law on the device: the repeated
+    advice point carries v^a and v^b and W_1 = -W_0 carries u^(S-1) and
+    u^(S-2) with random v, u, so no two products coincide; those branches are
+    planted in tests/accum_edge_util.py."""
     po = sh.point_offsets()
     p0 = proofs[0]
     p0.points[po["W"][0]] = None                  # W_0 = identity
