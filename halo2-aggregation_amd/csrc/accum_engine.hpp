@@ -358,6 +358,17 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   for (uint32_t i = 0; i < s->n_perm_columns; i++) vk.insert(vk.end(), s->sigma_commitments + 8 * i, s->sigma_commitments + 8 * i + 8);
   vk.insert(vk.end(), s->g1, s->g1 + 8);
 
+  // k_acc_scalars' LDS: (nsc + T + exchange + work) rows of 32 B per proof
+  // (proof stride np + 1) and the tail (constants + program).  A shape whose
+  // rows do not fit is refused here, before anything is uploaded or launched
+  // (the check used to sit behind the ladder's launch, so the error returned
+  // with that kernel in flight and the VK tables invalidated)
+  const size_t row_bytes =
+      (size_t)(L.nsc + T + kAccXVals + acc_num_vals(h) + 2 * (h.bf + 3) + kAccStack + h.nslots + h.nh) * 32;
+  const size_t tail_bytes = (size_t)acc_scalars_tail_words(h) * 4;
+  if (tail_bytes + 2 * row_bytes > kAccScalarsLds)
+    return set_error(PM_ERR_UNSUPPORTED, "accum: too many evaluations / terms per proof");
+
   const hipStream_t st = ctx->stream;
   int rc;
   if ((rc = ctx->acc_prog.put(prog, st))) return rc;
@@ -464,14 +475,8 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   // status: the replay stores bits 0-1 per proof, k_acc_scalars ORs in the
   // denominator bit; without a replay the words start at zero
   if (d_status && !vk_repr) HIP_TRY(hipMemsetAsync(d_status, 0, B * sizeof(uint32_t), side));
-  // k_acc_scalars: 4 waves per block of np proofs, (nsc + T + exchange +
-  // work) rows of 32 B per proof in LDS (proof stride np + 1), np <= 64
-  // within a 128 KiB budget
-  const size_t row_bytes =
-      (size_t)(L.nsc + T + kAccXVals + acc_num_vals(h) + 2 * (h.bf + 3) + kAccStack + h.nslots + h.nh) * 32;
-  const size_t tail_bytes = (size_t)acc_scalars_tail_words(h) * 4;  // constants + program
-  if (tail_bytes + 2 * row_bytes > kAccScalarsLds)
-    return set_error(PM_ERR_UNSUPPORTED, "accum: too many evaluations / terms per proof");
+  // k_acc_scalars: 4 waves per block of np proofs (row_bytes / tail_bytes
+  // above, checked against kAccScalarsLds before the first launch)
   // 16 proofs per block (round 5): wave 0 then runs the Lagrange chain with a
   // quad per proof (acc_lagrange_q, ~half the one-lane chain); more blocks
   // only spread the batch over more CUs

@@ -168,6 +168,13 @@ class ProofShape:
 
     @property
     def n_perm_sets(self):
+        """Chunks of the permutation argument (permutation.rs:62-69: one Z per
+        chunk of cs.degree() - 2 columns); none without permutation columns,
+        whatever the chunk length (0 is legal then)."""
+        if not self.perm_columns:
+            return 0
+        if self.perm_chunk_len <= 0:
+            raise ValueError("perm_chunk_len = 0 with permutation columns")
         return (len(self.perm_columns) + self.perm_chunk_len - 1) // self.perm_chunk_len
 
     # per-proof point layout
@@ -306,8 +313,16 @@ def lagrange_evals(r, shape, x, xn):
 
 
 def permutation_expressions(r, shape, d, l_0, l_last, l_blind, beta, gamma, x):
-    """permutation.rs:190-324."""
+    """permutation.rs:190-324.  An empty argument (no permutation columns, so
+    no product commitment was read) contributes no identity.  The reference's
+    gadget indexes sets[0] (permutation.rs:218, assert at :225) and so cannot
+    run such a circuit; the rule is that of the verifier it restates [3P:
+    halo2 plonk/permutation/verifier.rs, Evaluated::expressions: every term
+    hangs off sets.first() / sets.last() / a set, so none is produced], which
+    is also what the C ABI (acc_perm_sets) and oracle/accum_ref.c do."""
     sets = d["perm_sets"]
+    if not sets:
+        return []
     exprs = [l_0 * (1 - sets[0]["eval"]) % r]
     zl = sets[-1]["eval"]
     exprs.append(l_last * (zl * zl - zl) % r)
