@@ -914,6 +914,7 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
 #include "poly_engine.hpp"
 #include "gp_engine.hpp"
 #include "domain_engine.hpp"
+#include "quotient_engine.hpp"
 
 // Explicit instantiations are visible to both compilation passes, so the
 // device pass instantiates every kernel the host driver launches; the op
@@ -932,7 +933,8 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
                          &msm_start_impl<Cv>, &msm_finish_impl<Cv>, &msm_small_impl<Cv>,         \
                          &many_table_impl<Cv>, &msm_many_impl<Cv>, &points_sum_impl<typename Cv::Base>, \
                          &poly_eval_impl<Cv>, &poly_witness_impl<Cv>, &grand_product_impl<Cv>,          \
-                         &domain_tables_impl<Cv>, &domain_run_impl<Cv>};
+                         &domain_tables_impl<Cv>, &domain_run_impl<Cv>, &quotient_seed_impl<Cv>,      \
+                         &quotient_run_impl<Cv>, &quotient_eval_host_impl<Cv>};
 #endif
 #define PM_DEFINE_CURVE_OPS(Cv, name)                                                          \
   namespace pm {                                                                               \
@@ -970,5 +972,10 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
   template int domain_tables_impl<Cv>(uint32_t, uint32_t, const uint64_t*, const uint64_t*, pm_domain*,        \
                                       std::vector<uint64_t>*);                                   \
   template int domain_run_impl<Cv>(Ctx*, const DomJob*);                                         \
+  template int quotient_seed_impl<Cv>(const pm_domain*, uint64_t*);                              \
+  template int quotient_run_impl<Cv>(Ctx*, const pm_quotient*, const void* const*, const uint64_t*, uint32_t, \
+                                     void*);                                                     \
+  template int quotient_eval_host_impl<Cv>(const pm_proof_shape*, size_t, const uint64_t*, const uint64_t*, \
+                                           const uint64_t*, uint64_t*);                          \
   PM_OPS_TABLE(Cv, name)                                                                       \
   }

@@ -1621,6 +1621,154 @@ int pm_extended_to_coeff(pm_ctx* ctx, const pm_domain* d, const uint64_t* evals,
   return PM_OK;
 }
 
+// ------------------------------------------------- quotient numerator (§8f-8)
+int pm_quotient_release(pm_quotient* q) {
+  if (!q) return PM_OK;
+  (void)hipSetDevice(q->device);
+  for (void* p : {q->d_prog, q->d_leaves, q->d_t, q->d_own})
+    if (p) (void)hipFree(p);
+  delete q;
+  return PM_OK;
+}
+
+namespace {
+// test hook (as PM_NTT_PASSES): the slot bound under which repeated leaves stay resident, 0 = every use loads
+uint32_t quot_cache_slots() {
+  const char* e = std::getenv("PM_QUOT_CACHE_SLOTS");
+  if (!e || !*e) return pm::kQuotCacheSlots;
+  return (uint32_t)std::min<long>(std::max<long>(std::atol(e), 0), pm::kQuotMaxSlots);
+}
+
+// the quotient's buffers: program, leaf table, t, and its own columns (with the context's mutex held)
+int quotient_build_locked(pm_ctx* ctx, const pm_domain* d, const pm_proof_shape* shape, pm_quotient* q) {
+  const CurveOps* ops = curve_ops(d->curve);
+  const pm::QuotPlan& pl = q->plan;
+  const uint32_t e = d->ext_k - d->k, bf = shape->blinding_factors;
+  const size_t n = (size_t)1 << d->k, N = (size_t)1 << d->ext_k, tl = (size_t)1 << e;
+  const hipStream_t st = ctx->stream;
+  int rc = ctx->begin_call();
+  if (rc) return rc;
+  std::vector<uint32_t> leaves(2 * pl.leaves.size() + 2, 0);
+  for (size_t i = 0; i < pl.leaves.size(); i++) {
+    leaves[2 * i] = pl.group_base[pl.leaves[i].kind] + pl.leaves[i].index;
+    leaves[2 * i + 1] = (uint32_t)(((int64_t)pl.leaves[i].rot * ((int64_t)1 << e)) & (int64_t)(N - 1));
+  }
+  const size_t ncols = pl.need_x ? pm::kQownCols : pl.need_l ? pm::kQownX : 0;
+  HIP_TRY(hipMalloc(&q->d_prog, pl.ops.size() * 4));
+  HIP_TRY(hipMalloc(&q->d_leaves, leaves.size() * 4));
+  HIP_TRY(hipMalloc(&q->d_t, tl * 32));
+  if (ncols) HIP_TRY(hipMalloc(&q->d_own, ncols * N * 32));
+  q->device_bytes = pl.ops.size() * 4 + leaves.size() * 4 + tl * 32 + ncols * N * 32;
+  HIP_TRY(hipMemcpyAsync(q->d_prog, pl.ops.data(), pl.ops.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(q->d_leaves, leaves.data(), leaves.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(q->d_t, (const char*)d->d_tab + (size_t)pm::kDomTabHead * 32, tl * 32, hipMemcpyDeviceToDevice,
+                         st));
+  if (!ncols) {
+    HIP_TRY(hipStreamSynchronize(st));
+    return PM_OK;
+  }
+  // unit vectors of the Lagrange basis, in the native form (x 2^261, so the columns need no
+  // repair in a product): row 0; row n - bf - 1; rows n - bf - 1 .. n - 1; and X as a polynomial
+  uint64_t seed[16];
+  if ((rc = ops->quotient_seed(d, seed))) return rc;
+  char* own = (char*)q->d_own;
+  std::vector<uint64_t> ones(4 * ((size_t)bf + 1));
+  for (size_t i = 0; i < ones.size(); i++) ones[i] = seed[8 + (i & 3)];
+  for (size_t c = 0; c < ncols; c++) HIP_TRY(hipMemsetAsync(own + c * N * 32, 0, n * 32, st));
+  HIP_TRY(hipMemcpyAsync(own + pm::kQownL0 * N * 32, ones.data(), 32, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(own + pm::kQownLast * N * 32 + (n - bf - 1) * 32, ones.data(), 32, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(own + pm::kQownSum * N * 32 + (n - bf - 1) * 32, ones.data(), ones.size() * 8,
+                         hipMemcpyHostToDevice, st));
+  if (pl.need_x) HIP_TRY(hipMemcpyAsync(own + pm::kQownX * N * 32 + 32, seed + 12, 32, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  void* ptrs[pm::kQownCols];
+  for (size_t c = 0; c < pm::kQownCols; c++) ptrs[c] = own + c * N * 32;
+  pm::DomJob job{};  // Lagrange -> coefficients: pm_fft_batch_device with omega^-1 and n^-1
+  job.op = pm::kDomOpFft;
+  job.curve = d->curve;
+  job.logn = d->k;
+  job.omega = seed;
+  job.scale = seed + 4;
+  job.d_out = ptrs;
+  job.C = pm::kQownX;
+  if ((rc = ops->domain_run(ctx, &job))) return rc;
+  return domain_run_locked(ctx, d, pm::kDomOpToExt, ptrs, ptrs, ncols, 0, 0);
+}
+}  // namespace
+
+int pm_quotient_create(pm_ctx* ctx, const pm_domain* d, const pm_proof_shape* shape, pm_quotient** out) {
+  if (!ctx || !d || !shape || !out) return set_error(PM_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (d->device != ctx->device) return set_error(PM_ERR_ARG, "the domain lives on another device");
+  if (shape->log_n != d->k) return set_error(PM_ERR_ARG, "shape.log_n differs from the domain's k");
+  if (std::memcmp(shape->omega, d->omega, 32)) return set_error(PM_ERR_ARG, "shape.omega differs from the domain's omega");
+  if (d->ext_k > pm::kQuotMaxLogN) return set_error(PM_ERR_UNSUPPORTED, "extended domain longer than 2^28");
+  std::unique_ptr<pm_quotient> q(new pm_quotient{});
+  AccLayout L;
+  bool unsupported = false;
+  const std::string err =
+      pm::quot_compile(shape, (int)(d->ext_k - d->k), d->ext_k, quot_cache_slots(), &q->plan, &L, &unsupported);
+  if (!err.empty()) return set_error(unsupported ? PM_ERR_UNSUPPORTED : PM_ERR_ARG, "quotient: " + err);
+  if (((uint64_t)1 << d->k) < (uint64_t)shape->blinding_factors + 2)
+    return set_error(PM_ERR_ARG, "quotient: fewer rows than blinding_factors + 2");
+  q->curve = d->curve;
+  q->device = ctx->device;
+  q->k = d->k;
+  q->ext_k = d->ext_k;
+  if (shape->n_constants) q->shape_consts.assign(shape->constants, shape->constants + 4 * (size_t)shape->n_constants);
+  std::memcpy(q->delta, shape->delta, 32);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const int rc = quotient_build_locked(ctx, d, shape, q.get());
+  if (rc) {
+    pm_quotient_release(q.release());
+    return rc;
+  }
+  *out = q.release();
+  return PM_OK;
+}
+
+int pm_quotient_info(const pm_quotient* q, uint32_t* n_expressions, uint32_t* products_per_row, uint32_t* loads_per_row,
+                     uint32_t* slots, size_t* device_bytes) {
+  if (!q) return set_error(PM_ERR_ARG, "null argument");
+  if (n_expressions) *n_expressions = q->plan.n_expr;
+  if (products_per_row) *products_per_row = q->plan.products;
+  if (loads_per_row) *loads_per_row = q->plan.loads;
+  if (slots) *slots = q->plan.slots;
+  if (device_bytes) *device_bytes = q->device_bytes;
+  return PM_OK;
+}
+
+int pm_quotient_device(pm_ctx* ctx, const pm_quotient* q, const pm_quotient_columns* cols, const uint64_t challenges[16],
+                       uint32_t flags, void* d_out) {
+  if (!ctx || !q || !cols || !challenges || !d_out) return set_error(PM_ERR_ARG, "null argument");
+  if (q->device != ctx->device) return set_error(PM_ERR_ARG, "the quotient lives on another device");
+  if (flags & ~(uint32_t)(PM_QUOT_DIVIDE_VANISHING | PM_QUOT_ACCUMULATE)) return set_error(PM_ERR_ARG, "unknown flag bits");
+  const void* const* groups[pm::kQlOwn] = {cols->advice, cols->fixed,    cols->instance, cols->sigma,
+                                           cols->perm_z, cols->lookup_a, cols->lookup_s, cols->lookup_z};
+  const uint32_t* base = q->plan.group_base;
+  std::vector<const void*> ptrs(base[pm::kQlOwn] + 1);
+  for (uint32_t g = 0; g < pm::kQlOwn; g++) {
+    const uint32_t cnt = base[g + 1] - base[g];
+    if (cnt && !groups[g]) return set_error(PM_ERR_ARG, "null column array");
+    for (uint32_t i = 0; i < cnt; i++) {
+      if (!groups[g][i]) return set_error(PM_ERR_ARG, "null column pointer");
+      ptrs[base[g] + i] = groups[g][i];
+    }
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const int rc = ctx->begin_call();
+  if (rc) return rc;
+  return curve_ops(q->curve)->quotient_run(ctx, q, ptrs.data(), challenges, flags, d_out);
+}
+
+int pm_quotient_eval_host(int curve, const pm_proof_shape* shape, size_t R, const uint64_t* scalars, const uint64_t* x,
+                          const uint64_t* challenges, uint64_t* out) {
+  if (!shape || (R && (!scalars || !x || !challenges || !out))) return set_error(PM_ERR_ARG, "null argument");
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return set_error(PM_ERR_ARG, "unknown curve id");
+  return ops->quotient_eval_host(shape, R, scalars, x, challenges, out);
+}
+
 // ------------------------------------------------- fixed-base MSM (§8f-3)
 static int fixed_create(pm_ctx* ctx, int curve, const void* bases, bool host, size_t n, int c, int rows,
                         pm_fixed_bases** out) {

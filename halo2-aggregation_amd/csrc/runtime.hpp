@@ -9,6 +9,7 @@
 
 #include "../../include/pasta_msm.h"
 #include "dropin_digest.hpp"
+#include "quotient_plan.hpp"
 
 #include <condition_variable>
 #include <cstring>
@@ -185,6 +186,25 @@ struct pm_domain {
   void* d_tab;
 };
 
+// Quotient numerator of one (domain, shape) pair (pm_quotient_create,
+// quotient_engine.hpp): the compiled program and what its constants read from
+// the shape (copied: the caller's shape need not outlive the call), and the
+// device buffers the quotient owns: program, leaf table, a copy of the
+// domain's t table, and the l_0 / l_last / l_last + l_blind / X columns.
+struct pm_quotient {
+  int curve;
+  int device;
+  uint32_t k, ext_k;
+  pm::QuotPlan plan;
+  std::vector<uint64_t> shape_consts;
+  uint64_t delta[4];
+  void* d_prog;
+  void* d_leaves;
+  void* d_t;
+  void* d_own;  // kQownCols columns of N scalars (those the program reads are filled)
+  size_t device_bytes;
+};
+
 namespace pm {
 // multiples table of a resident base set (msm_many.hpp): entry (i, w, m) =
 // [m 2^{c w}] P_i, m = 1 .. H = 2^(c-1), w < W, XYZZ R = 2^261 (128 B), for
@@ -224,6 +244,7 @@ constexpr uint32_t kGpInvert = 0x80000000u;
 enum : int { kDomOpFft = 0, kDomOpToExt = 1, kDomOpToCoeff = 2, kDomOpDivide = 3 };
 constexpr uint32_t kDomDivideVanishing = 1u;  // PM_EXT_DIVIDE_VANISHING
 constexpr uint32_t kDomMaxE = 8;              // extended_k - k
+constexpr int kDomTabHead = 6;                // entries of pm_domain::d_tab before t_0 (a quotient copies t)
 struct DomJob {
   int op, curve;
   uint32_t logn;              // transform length (extended_k of dom, or log_n of the batched NTT)
@@ -301,6 +322,8 @@ struct pm_ctx {
   pm::Buf gp_rows;
   // extended-domain conversions (domain_engine.hpp): the call's column pointer tables
   pm::Buf dom_ptrs;
+  // quotient numerator (quotient_engine.hpp): the call's pointer table and constants
+  pm::Buf quot_io;
   // the power table of the last omega a grand product named: one prover calls with one omega, and the
   // table's chain of squarings is pure latency (0.04 ms of a 2^20 call); valid while gp_tab.gen == gp_tab_gen
   pm::Buf gp_tab;
@@ -346,7 +369,7 @@ struct pm_ctx {
   std::vector<pm::Buf*> all_bufs() {
     return {&in_scalars, &in_scalars2, &in_bases, &digits, &sorted, &counts, &offsets, &cursor,
             &bsum,       &buckets,  &head,   &segS,   &segT,   &bits,    &win, &longs, &mid,
-            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1], &poly_job, &poly_tab, &poly_aux, &poly_q, &gp_rows, &gp_tab, &dom_ptrs};
+            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1], &poly_job, &poly_tab, &poly_aux, &poly_q, &gp_rows, &gp_tab, &dom_ptrs, &quot_io};
   }
   ~pm_ctx();
   int begin_call();
@@ -438,6 +461,14 @@ struct CurveOps {
   int (*domain_tables)(uint32_t k, uint32_t ext_k, const uint64_t* omega_e, const uint64_t* zeta, pm_domain* d,
                        std::vector<uint64_t>* tab);
   int (*domain_run)(Ctx* ctx, const DomJob* job);
+  // quotient numerator (quotient_engine.hpp): the field values pm_quotient_create
+  // seeds the quotient's own columns with; one evaluation over the extended
+  // domain; the compiled program on the CPU
+  int (*quotient_seed)(const pm_domain* d, uint64_t* out);
+  int (*quotient_run)(Ctx* ctx, const pm_quotient* q, const void* const* ptrs, const uint64_t* challenges,
+                      uint32_t flags, void* d_out);
+  int (*quotient_eval_host)(const pm_proof_shape* shape, size_t R, const uint64_t* scalars, const uint64_t* x,
+                            const uint64_t* challenges, uint64_t* out);
 };
 extern const CurveOps kPallasOps, kVestaOps, kBn254Ops;
 

@@ -70,6 +70,14 @@ GP_OMEGA = 0xFFFFFFFE
 GP_CHAIN = 1
 GP_MAX_FACTORS = 16
 EXT_DIVIDE_VANISHING = 1  # PM_EXT_DIVIDE_VANISHING
+QUOT_DIVIDE_VANISHING = 1  # PM_QUOT_DIVIDE_VANISHING
+QUOT_ACCUMULATE = 2  # PM_QUOT_ACCUMULATE
+QUOT_GROUPS = ("advice", "fixed", "instance", "sigma", "perm_z", "lookup_a", "lookup_s", "lookup_z")
+
+
+class PmQuotientColumns(ctypes.Structure):
+    """pm_quotient_columns: host arrays of device pointers, one array per group."""
+    _fields_ = [(g, ctypes.POINTER(ctypes.c_void_p)) for g in QUOT_GROUPS]
 
 
 class PmGpFactor(ctypes.Structure):
@@ -338,6 +346,13 @@ def _load():
                                  _u64p], ctypes.c_int),
         "pm_coeff_to_extended": ([_vp, _vp, _u64p, _u64p], ctypes.c_int),
         "pm_extended_to_coeff": ([_vp, _vp, _u64p, ctypes.c_size_t, ctypes.c_uint32, _u64p], ctypes.c_int),
+        "pm_quotient_create": ([_vp, _vp, ctypes.POINTER(PmProofShape), ctypes.POINTER(_vp)], ctypes.c_int),
+        "pm_quotient_info": ([_vp, _u32p, _u32p, _u32p, _u32p, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+        "pm_quotient_release": ([_vp], ctypes.c_int),
+        "pm_quotient_device": ([_vp, _vp, ctypes.POINTER(PmQuotientColumns), _u64p, ctypes.c_uint32, _vp],
+                               ctypes.c_int),
+        "pm_quotient_eval_host": ([ctypes.c_int, ctypes.POINTER(PmProofShape), ctypes.c_size_t, _u64p, _u64p, _u64p,
+                                   _u64p], ctypes.c_int),
         "pm_vk_transcript_repr": ([ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, _u64p], ctypes.c_int),
         "pm_transcript_batch": ([_vp, ctypes.c_int, ctypes.POINTER(PmProofShape), ctypes.c_size_t, _u64p, _u64p,
                                  _u64p, _u64p, _u32p], ctypes.c_int),
@@ -615,6 +630,68 @@ class Domain:
             self.release()
         except Exception:
             pass
+
+
+def quotient_column_counts(shape: ProofShape):
+    """Columns per group of pm_quotient_columns for a shape, in QUOT_GROUPS order."""
+    s = shape.c
+    nps = (s.n_perm_columns + s.perm_chunk_len - 1) // s.perm_chunk_len if s.perm_chunk_len else 0
+    return dict(zip(QUOT_GROUPS, (s.num_advice_columns, s.num_fixed_columns, s.num_instance_columns, s.n_perm_columns,
+                                  nps, s.num_lookups, s.num_lookups, s.num_lookups)))
+
+
+class Quotient:
+    """pm_quotient: the quotient numerator of one (domain, shape) pair, compiled
+    to a program for k_quot_eval, with the l_0 / l_last / l_blind / X columns it
+    owns on the context's device."""
+
+    def __init__(self, ctx, dom, shape: ProofShape):
+        self.h = None
+        if shape.curve != dom.curve:
+            raise ValueError("the shape and the domain are of different curves")
+        if shape.c.log_n != dom.k:
+            raise ValueError("shape.log_n differs from the domain's k")
+        h = _vp()
+        _check(lib().pm_quotient_create(ctx.h, dom.h, ctypes.byref(shape.c), ctypes.byref(h)))
+        self.h = h
+        self.curve, self.N = dom.curve, dom.N
+        self.counts = quotient_column_counts(shape)
+
+    def info(self):
+        """dict: n_expressions, products_per_row, loads_per_row, slots, device_bytes"""
+        v = [ctypes.c_uint32(0) for _ in range(4)]
+        b = ctypes.c_size_t(0)
+        _check(lib().pm_quotient_info(self.h, *[ctypes.byref(x) for x in v], ctypes.byref(b)))
+        return dict(n_expressions=v[0].value, products_per_row=v[1].value, loads_per_row=v[2].value,
+                    slots=v[3].value, device_bytes=b.value)
+
+    def release(self):
+        if self.h is not None:
+            lib().pm_quotient_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def quotient_eval_host(shape: ProofShape, scalars, x, challenges):
+    """pm_quotient_eval_host: the compiled program on the CPU at R points.
+    scalars (R, scalars_per_proof, 4), x (R, 4), challenges (R, 16) [theta,
+    beta, gamma, y], u64 Montgomery -> (R, 4)."""
+    xs = _as_u64(x, 4)
+    R = xs.shape[0]
+    ch = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1)
+    sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1)
+    if ch.shape[0] != 16 * R:
+        raise ValueError("challenges must hold theta, beta, gamma, y (16 x u64) per point")
+    if sc.shape[0] != 4 * R * shape.layout()[1]:
+        raise ValueError("scalars must hold scalars_per_proof scalars (4 x u64 each) per point")
+    out = np.zeros((R, 4), dtype=np.uint64)
+    _check(lib().pm_quotient_eval_host(shape.curve, ctypes.byref(shape.c), R, _p(sc), _p(xs), _p(ch), _p(out)))
+    return out
 
 
 class Context:
@@ -1202,6 +1279,39 @@ class Context:
         _check(lib().pm_extended_to_coeff(self.h, dom.h, _p(a), keep,
                                           EXT_DIVIDE_VANISHING if divide_vanishing else 0, _p(out)))
         return out
+
+    # ---- quotient numerator (pm_quotient_*)
+    def quotient(self, dom: Domain, shape: ProofShape):
+        return Quotient(self, dom, shape)
+
+    def quotient_device(self, q: Quotient, cols, challenges, d_out, divide_vanishing=False, accumulate=False):
+        """pm_quotient_device: cols maps each group of QUOT_GROUPS to its
+        device pointers (q.N scalars per column; a group of no columns may be
+        left out), challenges = theta, beta, gamma, y as (4, 4) u64 Montgomery,
+        d_out receives q.N scalars and must not overlap an input column."""
+        unknown = set(cols) - set(QUOT_GROUPS)
+        if unknown:
+            raise ValueError("unknown column group(s): " + ", ".join(sorted(unknown)))
+        c = PmQuotientColumns()
+        keep = []
+        for g in QUOT_GROUPS:
+            ptrs = [int(p) for p in cols.get(g, ())]
+            if len(ptrs) != q.counts[g]:
+                raise ValueError(f"group {g}: {q.counts[g]} column pointers expected, {len(ptrs)} given")
+            if any(p == 0 for p in ptrs):
+                raise ValueError("null column pointer")
+            if int(d_out) in ptrs:
+                raise ValueError("d_out must not overlap an input column")
+            arr = (_vp * max(1, len(ptrs)))(*ptrs)
+            keep.append(arr)
+            setattr(c, g, ctypes.cast(arr, ctypes.POINTER(_vp)))
+        ch = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1)
+        if ch.shape[0] != 16:
+            raise ValueError("challenges are theta, beta, gamma, y (4 x 4 x u64)")
+        if not int(d_out):
+            raise ValueError("null output pointer")
+        flags = (QUOT_DIVIDE_VANISHING if divide_vanishing else 0) | (QUOT_ACCUMULATE if accumulate else 0)
+        _check(lib().pm_quotient_device(self.h, q.h, ctypes.byref(c), _p(ch), flags, _vp(int(d_out))))
 
     def selftest_field(self, curve, seed, n):
         m = ctypes.c_uint64(0)

@@ -687,6 +687,87 @@ int pm_coeff_to_extended(pm_ctx* ctx, const pm_domain* d, const uint64_t* coeffs
 int pm_extended_to_coeff(pm_ctx* ctx, const pm_domain* d, const uint64_t* evals, size_t keep, uint32_t flags,
                          uint64_t* out);
 
+/* ---- Quotient numerator on the extended domain ---------------
+ * halo2 `evaluate_h`, the input of `vanishing::Argument::construct` [3P
+ * plonk/prover.rs]: the step of create_proof between
+ * pm_coeff_to_extended_device (every column on the coset) and
+ * pm_extended_to_coeff_device (h back to coefficients).  With n = 2^k,
+ * N = 2^extended_k, e = extended_k - k and X_j = zeta omega_e^j of the domain,
+ * for every 0 <= j < N
+ *     out[j] = fold(exprs_j),   h = exprs[0]; for each later expression: h = h y + expr
+ * where exprs_j is the list of the verifier's identities (verifier.rs:593-643:
+ * the gates, permutation.rs:190-324, lookup.rs:173-311, in that order; the
+ * list oracle/accum.py::scalar_block builds) at x = X_j with every evaluation
+ * replaced by a read of the column's extended form col[j] = p(X_j):
+ *   rotation rule: a query (column, rot) at row j reads
+ *     col[(j + rot 2^e) mod N], which is p(omega^rot X_j); rot may be negative.
+ *   The permutation product Z of set i is read at rot 0, 1 and
+ *     -(blinding_factors + 1); a lookup's Z at rot 0 and 1, its permuted input
+ *     A' at rot 0 and -1, its permuted table S' at rot 0; a sigma column at
+ *     rot 0; a permutation column through its query index, whatever that
+ *     query's rotation.  l_0, l_last and l_blind are the Lagrange polynomials
+ *     of rows 0, n - blinding_factors - 1 and the rows after it, at X_j.
+ *   The lookup compress runs over the flattened expression lists, and an empty
+ *     permutation argument contributes no identity, as in the accumulator.
+ * There is no division by X^n - 1 unless PM_QUOT_DIVIDE_VANISHING asks for it.
+ *
+ * pm_quotient_create compiles the shape into one linear program for the
+ *   domain (checked on the host before the device is touched), and builds
+ *   l_0, l_last, l_last + l_blind and X_j on the coset (pm_fft_batch_device
+ *   with omega^-1, pm_coeff_to_extended_device).  The quotient owns these
+ *   buffers (pm_quotient_info: device_bytes) and copies what it needs of the
+ *   shape and the domain, so neither has to outlive the call.  It belongs to
+ *   the context's device and may be used by any context of that device.
+ * pm_quotient_info: the number of folded expressions, field products and
+ *   column loads per extended row, value slots of the program and device
+ *   bytes owned (any output pointer may be NULL).
+ * pm_quotient_device: one launch, one canonical store per row.  The column
+ *   arrays are HOST arrays of DEVICE pointers to N scalars each; an array may
+ *   be NULL when its count is 0.  challenges: theta, beta, gamma, y.
+ *   no-overlap rule: d_out must not overlap any input column (a row reads
+ *   other rows of its inputs); no input is written.
+ *   PM_QUOT_DIVIDE_VANISHING: out[j] *= t[j mod 2^e] after the fold, the same
+ *     result as the plain call followed by pm_divide_by_vanishing_device.
+ *   PM_QUOT_ACCUMULATE: the fold starts from d_out[j] instead of 0, so the
+ *     expressions of several circuits fold into one h.
+ * pm_quotient_eval_host: the compiled program on the CPU at R independent
+ *   points.  scalars: R x scalars_per_proof x 4 in pm_shape_layout's per-proof
+ *   scalar order (the "rand" evaluation is ignored), x: R x 4, challenges:
+ *   R x 16, out: R x 4; l_0, l_last, l_blind from the closed form at x
+ *   (x^n = 1 is PM_ERR_ARG).  It needs no device.
+ * Every scalar is 4 x u64 Montgomery and canonical, in and out.
+ *
+ * PM_ERR_ARG, before the device is touched: a null context, domain, shape,
+ * quotient, columns or pointer; a null column pointer; shape.log_n != k;
+ * shape.omega != the domain's omega; a shape pm_shape_layout rejects; a shape
+ * with no expression at all; 2^k < blinding_factors + 2; unknown flag bits; a
+ * domain or quotient of another device.  PM_ERR_UNSUPPORTED: N > 2^28; a
+ * program longer than 65536 ops, leaves or constants; a program that needs
+ * more than 28 value slots (a gate of stack depth 16 needs 16, a lookup
+ * expression of that depth 19: every shape pm_shape_layout accepts fits). */
+typedef struct pm_quotient pm_quotient;
+typedef struct pm_quotient_columns {      /* HOST arrays of DEVICE pointers, N scalars each */
+  const void* const* advice;    /* shape.num_advice_columns   */
+  const void* const* fixed;     /* shape.num_fixed_columns    */
+  const void* const* instance;  /* shape.num_instance_columns */
+  const void* const* sigma;     /* shape.n_perm_columns       */
+  const void* const* perm_z;    /* permutation sets (ceil(n_perm_columns / perm_chunk_len)) */
+  const void* const* lookup_a;  /* permuted input A', shape.num_lookups */
+  const void* const* lookup_s;  /* permuted table S' */
+  const void* const* lookup_z;
+} pm_quotient_columns;
+#define PM_QUOT_DIVIDE_VANISHING 1u  /* out[j] *= t[j mod 2^e] after the fold */
+#define PM_QUOT_ACCUMULATE       2u  /* the fold starts from d_out[j] instead of 0 (several circuits into one h) */
+
+int pm_quotient_create(pm_ctx* ctx, const pm_domain* d, const pm_proof_shape* shape, pm_quotient** out);
+int pm_quotient_info(const pm_quotient* q, uint32_t* n_expressions, uint32_t* products_per_row,
+                     uint32_t* loads_per_row, uint32_t* slots, size_t* device_bytes);
+int pm_quotient_release(pm_quotient* q);   /* NULL is fine, as pm_domain_release */
+int pm_quotient_device(pm_ctx* ctx, const pm_quotient* q, const pm_quotient_columns* cols,
+                       const uint64_t challenges[16] /* theta, beta, gamma, y */, uint32_t flags, void* d_out /* N */);
+int pm_quotient_eval_host(int curve, const pm_proof_shape* shape, size_t R, const uint64_t* scalars,
+                          const uint64_t* x, const uint64_t* challenges, uint64_t* out);
+
 /* ---- Blake2b transcript replay ------------------------------
  * The verifier squeezes theta, beta, gamma, y, x, v, u from a halo2
  * Blake2bWrite/Challenge255 transcript (TranscriptChip,
