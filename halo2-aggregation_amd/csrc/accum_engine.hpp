@@ -916,66 +916,62 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
 #include "domain_engine.hpp"
 #include "quotient_engine.hpp"
 
-// Explicit instantiations are visible to both compilation passes, so the
-// device pass instantiates every kernel the host driver launches; the op
-// table (host function pointers) exists only in the host pass.
+// One place per engine entry: make_curve_ops fills the table by member name.
+// Its explicit instantiation is visible to both compilation passes, so the
+// device pass instantiates every kernel the entries launch; the table itself
+// (host function pointers) exists only in the host pass.  The two entries that
+// other entries call are instantiated explicitly after it: their kernels are
+// then emitted behind all others instead of inside their first caller's, which
+// keeps the MSM and accumulator kernels byte for byte at the addresses they
+// had (and were measured at) under the earlier list of explicit instantiations.
+namespace pm {
+template <class Cv>
+CurveOps make_curve_ops() {
+  using F = typename Cv::Base;
+  CurveOps o{};
+  o.msm = &msm_device_to_aff<Cv>;
+  o.synth_scalars = &synth_scalars_impl<Cv>;
+  o.synth_bases = &synth_bases_impl<Cv>;
+  o.accum = &accum_device_entry<Cv>;
+  o.proofs = &proofs_device_impl<Cv>;
+  o.selftest_field = &selftest_field_impl<Cv>;
+  o.fixed_table = &fixed_table_impl<Cv>;
+  o.ntt = &ntt_device_impl<Cv>;
+  o.msm_fixed = &msm_fixed_to_aff<Cv>;
+  o.bases_to29 = &bases_to29_impl<Cv>;
+  o.msm_resident_batch = &msm_resident_batch_impl<Cv>;
+  o.transcript = &transcript_device_impl<Cv>;
+  o.msm_start = &msm_start_impl<Cv>;
+  o.msm_finish = &msm_finish_impl<Cv>;
+  o.msm_small = &msm_small_impl<Cv>;
+  o.many_table = &many_table_impl<Cv>;
+  o.msm_many = &msm_many_impl<Cv>;
+  o.poly_eval = &poly_eval_impl<Cv>;
+  o.poly_witness = &poly_witness_impl<Cv>;
+  o.grand_product = &grand_product_impl<Cv>;
+  o.domain_tables = &domain_tables_impl<Cv>;
+  o.domain_run = &domain_run_impl<Cv>;
+  o.quotient_seed = &quotient_seed_impl<Cv>;
+  o.quotient_run = &quotient_run_impl<Cv>;
+  o.quotient_eval_host = &quotient_eval_host_impl<Cv>;
+  // host only
+  o.point_add = &point_add_impl<F>;
+  o.points_sum = &points_sum_impl<F>;
+  o.vk_repr = &vk_repr_impl<Cv>;
+  return o;
+}
+}  // namespace pm
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PM_OPS_TABLE(Cv, name)
 #else
-#define PM_OPS_TABLE(Cv, name)                                                                 \
-  extern const CurveOps name;                                                                  \
-  const CurveOps name = {&msm_device_to_aff<Cv>, &point_add_impl<typename Cv::Base>,            \
-                         &synth_scalars_impl<Cv>, &synth_bases_impl<Cv>,  \
-                         &accum_device_entry<Cv>, &selftest_field_impl<Cv>,           \
-                         &transcript_device_impl<Cv>, &vk_repr_impl<Cv>,                   \
-                         &fixed_table_impl<Cv>, &ntt_device_impl<Cv>, &msm_fixed_to_aff<Cv>,    \
-                         &bases_to29_impl<Cv>, &msm_resident_batch_impl<Cv>, &proofs_device_impl<Cv>,    \
-                         &msm_start_impl<Cv>, &msm_finish_impl<Cv>, &msm_small_impl<Cv>,         \
-                         &many_table_impl<Cv>, &msm_many_impl<Cv>, &points_sum_impl<typename Cv::Base>, \
-                         &poly_eval_impl<Cv>, &poly_witness_impl<Cv>, &grand_product_impl<Cv>,          \
-                         &domain_tables_impl<Cv>, &domain_run_impl<Cv>, &quotient_seed_impl<Cv>,      \
-                         &quotient_run_impl<Cv>, &quotient_eval_host_impl<Cv>};
+#define PM_OPS_TABLE(Cv, name) const CurveOps name = make_curve_ops<Cv>();
 #endif
-#define PM_DEFINE_CURVE_OPS(Cv, name)                                                          \
-  namespace pm {                                                                               \
-  template int msm_device_to_aff<Cv>(Ctx*, const void*, const void*, size_t, uint32_t, uint64_t*, const void*); \
-  template int synth_scalars_impl<Cv>(Ctx*, uint64_t, uint64_t, uint32_t, uint32_t, void*);     \
-  template int synth_bases_impl<Cv>(Ctx*, uint64_t, uint64_t, uint32_t, void*);                 \
-  template int accum_device_entry<Cv>(Ctx*, const pm_proof_shape*, size_t, const void*, const void*, void*, void*, \
-                                      void*, const uint64_t*, void*);                            \
-  template int proofs_device_impl<Cv>(Ctx*, const pm_proof_shape*, size_t, const void*, size_t, const void*, void*, \
-                                      void*, void*, const uint64_t*, void*, void*, void*);       \
-  template int selftest_field_impl<Cv>(Ctx*, uint64_t, uint32_t, uint64_t*);                      \
-  template int fixed_table_impl<Cv>(Ctx*, const void*, pm_fixed_bases*);                          \
-  template int ntt_device_impl<Cv>(Ctx*, int, void*, uint32_t, const uint64_t*, const uint64_t*);  \
-  template int msm_fixed_to_aff<Cv>(Ctx*, const pm_fixed_bases*, const void*, size_t, uint32_t, uint64_t*, \
-                                    const void*);                                                  \
-  template int bases_to29_impl<Cv>(Ctx*, const void*, size_t, void*);                            \
-  template int msm_resident_batch_impl<Cv>(Ctx*, const void*, const pm_fixed_bases*, const uint64_t* const*, size_t, \
-                                           size_t, uint32_t, uint64_t*);                             \
+#define PM_DEFINE_CURVE_OPS(Cv, name)            \
+  namespace pm {                                 \
+  template CurveOps make_curve_ops<Cv>();        \
+  template int bases_to29_impl<Cv>(Ctx*, const void*, size_t, void*); \
   template int transcript_device_impl<Cv>(Ctx*, const pm_proof_shape*, size_t, const uint64_t*, const void*, \
-                                          const void*, void*, void*);                            \
-  template int msm_start_impl<Cv>(Ctx*, const pm_fixed_bases*, const void*, const void*, size_t, uint32_t, void*, \
-                                  const void*); \
-  template int msm_finish_impl<Cv>(Ctx*, const void*, uint64_t*);                                \
-  template int msm_small_impl<Cv>(Ctx*, const void*, bool, const void*, bool, bool, size_t, uint32_t, uint64_t*); \
-  template int many_table_impl<Cv>(Ctx*, const void*, size_t, ManyTable*);                       \
-  template int msm_many_impl<Cv>(Ctx*, const ManyTable*, size_t, const size_t*, const size_t*, const void*, bool, \
-                                 uint32_t, uint64_t*);                                           \
-  template int poly_eval_impl<Cv>(Ctx*, const void* const*, size_t, size_t, const uint32_t*, const uint64_t*, size_t, \
-                                  uint64_t*);                                                    \
-  template int poly_witness_impl<Cv>(Ctx*, const void* const*, size_t, size_t, const uint32_t*, const uint32_t*, \
-                                     const uint64_t*, const uint64_t*, size_t, void*, uint64_t*); \
-  template int grand_product_impl<Cv>(Ctx*, int, const void* const*, size_t, size_t, const pm_gp_factor*, const uint32_t*, \
-                                      const pm_gp_factor*, const uint32_t*, size_t, const uint64_t*, const uint64_t*, \
-                                      size_t, uint32_t, void*, uint64_t*);                       \
-  template int domain_tables_impl<Cv>(uint32_t, uint32_t, const uint64_t*, const uint64_t*, pm_domain*,        \
-                                      std::vector<uint64_t>*);                                   \
-  template int domain_run_impl<Cv>(Ctx*, const DomJob*);                                         \
-  template int quotient_seed_impl<Cv>(const pm_domain*, uint64_t*);                              \
-  template int quotient_run_impl<Cv>(Ctx*, const pm_quotient*, const void* const*, const uint64_t*, uint32_t, \
-                                     void*);                                                     \
-  template int quotient_eval_host_impl<Cv>(const pm_proof_shape*, size_t, const uint64_t*, const uint64_t*, \
-                                           const uint64_t*, uint64_t*);                          \
-  PM_OPS_TABLE(Cv, name)                                                                       \
+                                          const void*, void*, void*); \
+  PM_OPS_TABLE(Cv, name)                         \
   }

@@ -3,7 +3,7 @@
 // pm_divide_by_vanishing_device, pm_fft_batch_device).
 // Boundary: halo2 EvaluationDomain::{coeff_to_extended, extended_to_coeff,
 // divide_by_vanishing_poly} [3P poly/domain.rs], reached from create_proof's
-// quotient step.  Arguments are validated by the C-ABI (capi.hip) before
+// quotient step.  Arguments are validated by the C-ABI (capi_poly.hip) before
 // domain_run_impl runs; domain_tables_impl is the part of that validation
 // that needs field arithmetic, and runs on the host alone.
 #pragma once
@@ -88,7 +88,7 @@ int domain_run_impl(Ctx* ctx, const DomJob* jp) {
   const uint32_t logn = j.logn;
   const size_t N = (size_t)1 << logn, C = j.C;
   const size_t stride = 8 * N;  // words per scratch row
-  const uint32_t* dtab = j.dom ? (const uint32_t*)j.dom->d_tab : nullptr;
+  const uint32_t* dtab = j.dom ? (const uint32_t*)j.dom->d_tab.p : nullptr;
   const uint32_t e = j.dom ? j.dom->ext_k - j.dom->k : 0;
   const int passes = logn <= (uint32_t)kNttOnePassLog ? 1 : ntt_passes(ctx, logn);
   // every buffer is sized before the first launch is queued

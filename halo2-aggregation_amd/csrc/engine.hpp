@@ -205,7 +205,7 @@ int msm_device_impl(Ctx* ctx, const uint32_t* d_scalars, const uint32_t* d_bases
   // histogram 0.048 -> 0.082 ms concurrently).
   const uint32_t* bases29;
   if (fixed) {
-    bases29 = (const uint32_t*)ft->d;
+    bases29 = (const uint32_t*)ft->d.p;
   } else if (pre29) {
     bases29 = d_bases;
   } else {
@@ -918,6 +918,7 @@ int msm_resident_batch_impl(Ctx* ctx, const void* d_bases29, const pm_fixed_base
 
 // Build a fixed-base table (pm_fixed_bases_create): ft->n, ft->c set by the
 // caller; fills W, npad and the device table.
+static_assert(kFixedPad == kSortB && kLdsPerCu == kMaxLds, "runtime.hpp's copies of the kernels' geometry");
 template <class Cv>
 int fixed_table_impl(Ctx* ctx, const void* d_bases, pm_fixed_bases* ft) {
   using F = typename Cv::Base;
@@ -931,10 +932,10 @@ int fixed_table_impl(Ctx* ctx, const void* d_bases, pm_fixed_bases* ft) {
     return set_error(PM_ERR_ARG, "fewer table rows than windows needs equal window widths (256 % W == 0)");
   ft->npad = std::max<size_t>(kSortB, (ft->n + kSortB - 1) / kSortB * kSortB);
   const size_t bytes = (size_t)ft->rows * ft->npad * 64;
-  HIP_TRY(hipMalloc(&ft->d, bytes));
+  if (int rc = ft->d.ensure(bytes)) return rc;
   k_fixed_table<F><<<(unsigned)((ft->npad + 255) / 256), 256, 0, ctx->stream>>>(
       (const uint32_t*)d_bases, (uint32_t)ft->n, (uint32_t)ft->npad, pl.W, pl.base, pl.extra, ft->rows,
-      (uint32_t*)ft->d);
+      (uint32_t*)ft->d.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return PM_OK;

@@ -3,7 +3,7 @@
 // plonk/permutation/prover.rs::commit, plonk/lookup/prover.rs::commit_product
 // and ff::BatchInvert [3P], reached from create_proof
 // (examples/simple-example.rs:663-710).  Arguments are validated by the C-ABI
-// (capi.hip) before this runs.
+// (capi_poly.hip) before this runs.
 #pragma once
 #include <cstring>
 #include <vector>

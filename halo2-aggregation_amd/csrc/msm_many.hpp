@@ -209,8 +209,9 @@ int many_table_impl(Ctx* ctx, const void* d_bases29, size_t n, ManyTable* t) {
   const uint32_t c = many_pick_c(n), W = many_windows(c), H = 1u << (c - 1);
   const size_t bytes = n * many_bytes_per_base(c);
   if (bytes > kManyTabCap) return set_error(PM_ERR_UNSUPPORTED, "many-MSM table above its memory cap");
-  void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, std::max<size_t>(bytes, 128)));
+  Buf tab;
+  if (int rc = tab.ensure(bytes)) return rc;
+  void* const d = tab.p;
   const hipStream_t st = ctx->stream;
   k_many_pow<F><<<(unsigned)((n + 255) / 256), 256, 0, st>>>((const uint32_t*)d_bases29, (uint32_t)n, c, W, H,
                                                              (Xyzz<F>*)d);
@@ -221,12 +222,9 @@ int many_table_impl(Ctx* ctx, const void* d_bases29, size_t n, ManyTable* t) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipFree(d);
+  if (e != hipSuccess)
     return set_error(PM_ERR_HIP, std::string("many-MSM table build: ") + hipGetErrorString(e));
-  }
-  if (t->d) (void)hipFree(t->d);
-  t->d = d;
+  t->d = std::move(tab);
   t->n = n;
   t->c = c;
   t->W = W;
@@ -359,7 +357,7 @@ int msm_many_impl(Ctx* ctx, const ManyTable* tb, size_t B, const size_t* n, cons
   void* dR = ctx->h_pinned_dev;
   uint32_t* dflag = (uint32_t*)((Xyzz<F>*)dR + msms.size());
   PM_LAUNCH(ctx, "many_sum",
-            (k_many_sum<Cv><<<(unsigned)jobs.size(), 256, 0, st>>>(g, djobs, dmsms, ds, (const Xyzz<F>*)tb->d,
+            (k_many_sum<Cv><<<(unsigned)jobs.size(), 256, 0, st>>>(g, djobs, dmsms, ds, (const Xyzz<F>*)tb->d.p,
                                                                    (Xyzz<F>*)ctx->small_part.p, tickets, (Xyzz<F>*)dR,
                                                                    dcount, dflag, seq)));
   hipEvent_t ev = ctx->grp_ev[0];

@@ -2,7 +2,7 @@
 // pm_multiopen_witness*).  Boundary: halo2 `eval_polynomial`,
 // `kate_division` [3P] and the witness loop of poly/multiopen/gwc/prover.rs
 // [3P], reached from create_proof (examples/simple-example.rs:606,702).
-// Arguments are validated by the C-ABI (capi.hip) before these run.
+// Arguments are validated by the C-ABI (capi_poly.hip) before these run.
 #pragma once
 #include <cstring>
 #include <vector>

@@ -1,7 +1,7 @@
 // quotient_engine.hpp -- host driver of the quotient numerator (pm_quotient_*,
 // SURVEY §8f-8): the per-call constant table, the launch of k_quot_eval, and
 // the program run on the CPU (pm_quotient_eval_host).  Arguments are validated
-// by the C-ABI (capi.hip), which also builds the quotient's own columns with
+// by the C-ABI (capi_poly.hip), which also builds the quotient's own columns with
 // pm_fft_batch_device / pm_coeff_to_extended_device's driver (domain_engine.hpp).
 #pragma once
 #include <cstring>
@@ -86,7 +86,7 @@ int quotient_run_impl(Ctx* ctx, const pm_quotient* q, const void* const* ptrs, c
   std::vector<const void*> host(n_ptrs);
   for (uint32_t i = 0; i < n_user; i++) host[i] = ptrs[i];
   for (uint32_t i = 0; i < kQownCols; i++)  // a gates-only program owns and reads none
-    host[n_user + i] = q->d_own ? (const char*)q->d_own + (size_t)i * N * 32 : nullptr;
+    host[n_user + i] = q->d_own.p ? (const char*)q->d_own.p + (size_t)i * N * 32 : nullptr;
   const size_t off_consts = (n_ptrs * sizeof(void*) + 31) / 32 * 32;
   int rc;
   if ((rc = ctx->quot_io.ensure(off_consts + consts.size() * 8))) return rc;
@@ -94,11 +94,11 @@ int quotient_run_impl(Ctx* ctx, const pm_quotient* q, const void* const* ptrs, c
   HIP_TRY(hipMemcpyAsync(base, host.data(), n_ptrs * sizeof(void*), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(base + off_consts, consts.data(), consts.size() * 8, hipMemcpyHostToDevice, st));
   QuotArgs a{};
-  a.prog = (const uint32_t*)q->d_prog;
-  a.leaves = (const uint32_t*)q->d_leaves;
+  a.prog = (const uint32_t*)q->d_prog.p;
+  a.leaves = (const uint32_t*)q->d_leaves.p;
   a.ptrs = (const uint32_t* const*)base;
   a.consts = (const uint32_t*)(base + off_consts);
-  a.t = (const uint32_t*)q->d_t;
+  a.t = (const uint32_t*)q->d_t.p;
   a.out = (uint32_t*)d_out;
   a.nops = (uint32_t)pl.ops.size();
   a.n = (uint32_t)N;

@@ -33,6 +33,11 @@ constexpr int kMaxC = 20;
 // in accumulate vs 6.1 ms at c = 16; at 2^20, c = 20 took 23.8 ms vs 1.4 ms.
 constexpr int kAutoMaxC = 16;
 constexpr size_t kMaxPoints = size_t(1) << 26;
+// what the host layer needs of the kernels' geometry without their headers
+// (engine.hpp checks both against msm_kernels.hpp): LDS per CU, and the point
+// count a fixed-base table row is padded to a multiple of
+constexpr size_t kLdsPerCu = 160 * 1024;
+constexpr size_t kFixedPad = 8192;
 constexpr int kL1 = 4;  // bucket-segment length of k_bucket_seg_q (one quad per segment)
 // internal msm flag (never in the public header; the C-ABI strips it from
 // caller flags): d_bases already hold the pipeline's R = 2^261 canonical
@@ -43,7 +48,7 @@ constexpr uint32_t kBasesR261 = 1u << 30;
 // extra lane also adds one tree addition (round 3 sweep of 4..64 / Wr at
 // 2^19-2^22, profiles/r03/ab/bits_split_sweep.jsonl: 16 best)
 constexpr int kBitsSplitK = 16;
-// drop-in base cache of pm_msm / pm_msm_ctx (capi.hip): base sets of at least
+// drop-in base cache of pm_msm / pm_msm_ctx (capi_dropin.hip): base sets of at least
 // kDropinMinN points are kept resident, keyed by a content digest; at most
 // kDropinEntries sets and kDropinBytes of device memory per context
 constexpr size_t kDropinMinN = size_t(1) << 12;
@@ -58,7 +63,7 @@ constexpr size_t kDropinFreeDiv = 2;
 // base sets seen once and not admitted: a set becomes resident on its second
 // sighting, so one-shot bases never pay the row-table build
 constexpr int kDropinSeen = 8;
-// small drop-in sets (multiples tables, capi.hip dropin_small_msm): at most
+// small drop-in sets (multiples tables, capi_dropin.hip dropin_small_msm): at most
 // this many, and this many bytes of tables, per context.  A table costs
 // 512 KiB per base at c = 8, so only sets of at most kDropinSmallMaxN points
 // are kept (512-point sets held 256 MiB each); their bytes count in
@@ -73,13 +78,45 @@ constexpr size_t kTailBytes = 128;  // opaque MsmTail storage (CurveOps::msm_sta
 constexpr size_t kSmallMaxN = PM_SMALL_MSM_DEFAULT;
 constexpr size_t kSmallLimit = PM_SMALL_MSM_LIMIT;
 
+// Grow-only device allocation that frees itself (on the device current at
+// destruction: the owners below set theirs first).  Move-only.
 struct Buf {
   void* p = nullptr;
   size_t cap = 0;
-  uint64_t gen = 0;  // bumped on every (re)allocation
+  uint64_t gen = 0;  // bumped whenever p changes: on every (re)allocation and on move assignment
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  Buf(Buf&& o) noexcept : p(o.p), cap(o.cap), gen(o.gen) { o.p = nullptr, o.cap = 0; }
+  Buf& operator=(Buf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, cap = o.cap, gen = (gen > o.gen ? gen : o.gen) + 1;
+      o.p = nullptr, o.cap = 0;
+    }
+    return *this;
+  }
+  ~Buf() { release(); }
   int ensure(size_t bytes);
-  void release();
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
 };
+inline int Buf::ensure(size_t bytes) {
+  if (bytes <= cap) return PM_OK;
+  release();
+  const size_t want = bytes < 256 ? 256 : bytes;
+  const hipError_t e = hipMalloc(&p, want);
+  if (e != hipSuccess) {
+    p = nullptr;
+    return set_error(PM_ERR_HIP, std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
+  }
+  cap = want;
+  gen++;
+  return PM_OK;
+}
 
 // Device copy of a small host table (accumulator / transcript programs,
 // constants, VK points) that is uploaded only when its bytes change: a batch
@@ -171,7 +208,7 @@ struct pm_fixed_bases {
   int device;
   int c, W, rows;
   size_t n, npad;
-  void* d;
+  pm::Buf d;
 };
 
 // Extended evaluation domain (pm_domain_create, domain_engine.hpp): the roots
@@ -183,7 +220,7 @@ struct pm_domain {
   int device;
   uint32_t k, ext_k;
   uint64_t omega[4], omega_e[4], omega_e_inv[4];
-  void* d_tab;
+  pm::Buf d_tab;
 };
 
 // Quotient numerator of one (domain, shape) pair (pm_quotient_create,
@@ -198,10 +235,8 @@ struct pm_quotient {
   pm::QuotPlan plan;
   std::vector<uint64_t> shape_consts;
   uint64_t delta[4];
-  void* d_prog;
-  void* d_leaves;
-  void* d_t;
-  void* d_own;  // kQownCols columns of N scalars (those the program reads are filled)
+  pm::Buf d_prog, d_leaves, d_t;
+  pm::Buf d_own;  // kQownCols columns of N scalars (those the program reads are filled)
   size_t device_bytes;
 };
 
@@ -211,7 +246,7 @@ namespace pm {
 // the first n bases; built on demand by pm_msm_resident_many* /
 // pm_bases_many_prepare and owned by the pm_bases
 struct ManyTable {
-  void* d = nullptr;
+  Buf d;
   size_t n = 0;
   uint32_t c = 0, W = 0, H = 0;
 };
@@ -366,11 +401,6 @@ struct pm_ctx {
   std::vector<pm::TimedSpan> pending;
   std::map<std::string, std::pair<uint64_t, double>> stats;
 
-  std::vector<pm::Buf*> all_bufs() {
-    return {&in_scalars, &in_scalars2, &in_bases, &digits, &sorted, &counts, &offsets, &cursor,
-            &bsum,       &buckets,  &head,   &segS,   &segT,   &bits,    &win, &longs, &mid,
-            &acc_prog.buf, &acc_const.buf, &acc_vk.buf, &acc_coef, &acc_part, &acc_io, &bases29, &tr_prog.buf, &tr_io, &bitsP, &tickets, &ntt_scratch, &bitsQ, &acc_lad, &acc_corr, &tr_canon, &ntt_scratch2, &acc_vkpow, &sqrt_tab[0], &sqrt_tab[1], &sqrt_tab[2], &pf_map.buf, &pf_io, &pf_flags, &small_tab, &small_dig, &small_part, &small_tk, &many_prog.buf, &tr_wtab.buf, &part_sorted[0], &part_sorted[1], &part_offsets[0], &part_offsets[1], &part_buckets[0], &part_buckets[1], &part_head[0], &part_head[1], &poly_job, &poly_tab, &poly_aux, &poly_q, &gp_rows, &gp_tab, &dom_ptrs, &quot_io};
-  }
   ~pm_ctx();
   int begin_call();
   int end_call();

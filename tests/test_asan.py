@@ -1,7 +1,7 @@
 """Host-side sanitizers, CPU only: ``make -C
 halo2-aggregation_amd asan`` builds
 
-* the C-ABI library's host code (capi.hip + the per-curve engine objects,
+* the C-ABI library's host code (the capi_*.hip units + the per-curve engine objects,
   host-only: plans, argument checks, shape validation, the MSM's host Horner,
   Blake2b) with clang ASan + UBSan -> lib_asan/libpasta_msm.so,
 * tests/native/host_asan.cpp (host_ec, inv_bgcd, blake2b, accum_plan) with

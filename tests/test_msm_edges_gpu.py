@@ -206,7 +206,7 @@ def test_rows8_prefix_and_offset(gpu_ctx, curve):
     """The same table over its first n / 2 + 17 points and over a window at
     offset 5, device and host scalars.  Both run the plain pipeline on row 0
     of the table: the offset window by rule, the prefix because it is shorter
-    than the row-table path's 2^18 points (resident_use_table in capi.hip; a
+    than the row-table path's 2^18 points (resident_use_table in capi_internal.hpp; a
     prefix that stays on the row table: test_rows4)."""
     inp = _rows8(gpu_ctx, curve)
     n, S, B, D = inp.n, inp.mixed.S, inp.B, inp.D
