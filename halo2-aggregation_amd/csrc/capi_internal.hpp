@@ -1,5 +1,5 @@
 // capi_internal.hpp -- what the units of the extern "C" boundary share
-// (capi_ctx / capi_msm / capi_dropin / capi_poly / capi_proofs /
+// (capi_ctx / capi_msm / capi_dropin / capi_poly / capi_lookup / capi_proofs /
 // capi_selftest .hip).  Host only: no kernel header is included here.
 #pragma once
 #include <cstring>

@@ -275,6 +275,9 @@ constexpr size_t kPolyMaxGridY = 65535;        // sets / pairs per call (grid.y)
 // grand products (gp_engine.hpp): the same limits; flag bit of CurveOps::grand_product
 // for the in-place batch inversion (never part of the C-ABI's flags)
 constexpr uint32_t kGpInvert = 0x80000000u;
+// lookup permuted columns (lookup_engine.hpp): rows as above; pairs and columns per call (2 P columns in grid.y)
+constexpr size_t kLkMaxPairs = PM_LOOKUP_MAX_PAIRS;
+constexpr size_t kLkMaxCols = PM_LOOKUP_MAX_COLS;
 // extended-domain conversions (domain_engine.hpp): one job of CurveOps::domain_run
 enum : int { kDomOpFft = 0, kDomOpToExt = 1, kDomOpToCoeff = 2, kDomOpDivide = 3 };
 constexpr uint32_t kDomDivideVanishing = 1u;  // PM_EXT_DIVIDE_VANISHING
@@ -355,6 +358,9 @@ struct pm_ctx {
   pm::Buf poly_job, poly_tab, poly_aux, poly_q;
   // grand products (gp_engine.hpp): the un-carried suffix products, S rows of n (the rest shares the three above)
   pm::Buf gp_rows;
+  // lookup permuted columns (lookup_engine.hpp): the call's pointer table, the two key buffers of the
+  // merge sort, and the pairing's row map, counts and flags
+  pm::Buf lk_job, lk_keys, lk_aux;
   // extended-domain conversions (domain_engine.hpp): the call's column pointer tables
   pm::Buf dom_ptrs;
   // quotient numerator (quotient_engine.hpp): the call's pointer table and constants
@@ -499,6 +505,11 @@ struct CurveOps {
                       uint32_t flags, void* d_out);
   int (*quotient_eval_host)(const pm_proof_shape* shape, size_t R, const uint64_t* scalars, const uint64_t* x,
                             const uint64_t* challenges, uint64_t* out);
+  // lookup permuted columns (lookup_engine.hpp): the theta-compression of m columns (theta may be null
+  // when m == 1); P (input, table) pairs sorted and paired, out_status P x (status, row) in host memory
+  int (*lookup_compress)(Ctx* ctx, const void* const* d_cols, size_t m, size_t n, const uint64_t* theta, void* d_out);
+  int (*lookup_permute)(Ctx* ctx, const void* const* d_a, const void* const* d_s, size_t P, size_t usable,
+                        void* const* d_out_a, void* const* d_out_s, uint32_t* out_status);
 };
 extern const CurveOps kPallasOps, kVestaOps, kBn254Ops;
 

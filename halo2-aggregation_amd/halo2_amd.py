@@ -69,6 +69,11 @@ GP_NONE = 0xFFFFFFFF
 GP_OMEGA = 0xFFFFFFFE
 GP_CHAIN = 1
 GP_MAX_FACTORS = 16
+LOOKUP_MAX_PAIRS = 32767  # PM_LOOKUP_MAX_PAIRS
+LOOKUP_MAX_COLS = 65535  # PM_LOOKUP_MAX_COLS
+LOOKUP_TILE = 2048  # PM_LOOKUP_TILE: keys sorted per block
+LOOKUP_MERGE = 2048  # PM_LOOKUP_MERGE: keys produced per merge block
+LOOKUP_MAX_N = 1 << 28
 EXT_DIVIDE_VANISHING = 1  # PM_EXT_DIVIDE_VANISHING
 QUOT_DIVIDE_VANISHING = 1  # PM_QUOT_DIVIDE_VANISHING
 QUOT_ACCUMULATE = 2  # PM_QUOT_ACCUMULATE
@@ -333,6 +338,13 @@ def _load():
                                      ctypes.POINTER(PmGpFactor), _u32p, ctypes.POINTER(PmGpFactor), _u32p,
                                      ctypes.c_size_t, _u64p, _u64p, ctypes.c_size_t, ctypes.c_uint32, _vp, _u64p],
                                     ctypes.c_int),
+        "pm_lookup_compress_device": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_size_t, ctypes.c_size_t,
+                                       _u64p, _vp], ctypes.c_int),
+        "pm_lookup_permute_device": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_size_t,
+                                      ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                      _u32p], ctypes.c_int),
+        "pm_lookup_permute": ([_vp, ctypes.c_int, _u64p, _u64p, ctypes.c_size_t, ctypes.c_size_t, _u64p, _u64p,
+                               _u32p], ctypes.c_int),
         "pm_domain_create": ([_vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p, ctypes.POINTER(_vp)],
                              ctypes.c_int),
         "pm_domain_info": ([_vp, _u32p, _u32p, _u64p, _u32p], ctypes.c_int),
@@ -1207,6 +1219,82 @@ class Context:
                                              active, GP_CHAIN if chain else 0, _vp(out_ptr),
                                              _p(last) if want_last else None))
         return last
+
+    # ---- lookup permuted columns (pm_lookup_compress_device / pm_lookup_permute*)
+    @staticmethod
+    def _lookup_rows(n, usable):
+        if not 1 <= n <= LOOKUP_MAX_N:
+            raise ValueError("n out of range (1 <= n <= 2^28)")
+        if not 1 <= usable <= n:
+            raise ValueError("usable out of range (1 <= usable <= n)")
+
+    def lookup_compress_device(self, curve, col_ptrs, n, theta, out_ptr):
+        """pm_lookup_compress_device: out[i] = sum_k theta^(m-1-k) col_k[i]
+        over the m device columns of n Montgomery scalars at col_ptrs; theta
+        (4,) u64 Montgomery, or None with one column (the output is then the
+        column).  out_ptr may be one of the columns."""
+        ptrs = [int(p) for p in col_ptrs]
+        if not 1 <= len(ptrs) <= LOOKUP_MAX_COLS:
+            raise ValueError("between 1 and 65535 columns")
+        if not 1 <= n <= LOOKUP_MAX_N:
+            raise ValueError("n out of range (1 <= n <= 2^28)")
+        if any(p == 0 for p in ptrs) or not int(out_ptr):
+            raise ValueError("null column pointer")
+        th = None
+        if theta is not None:
+            th = np.ascontiguousarray(theta, dtype=np.uint64).reshape(-1)
+            if th.shape[0] != 4:
+                raise ValueError("theta must be one scalar (4 x u64)")
+        elif len(ptrs) > 1:
+            raise ValueError("theta is None with more than one column")
+        arr, m = self._poly_ptrs(ptrs)
+        _check(lib().pm_lookup_compress_device(self.h, curve, arr, m, n, None if th is None else _p(th), _vp(out_ptr)))
+
+    def lookup_permute_device(self, curve, d_a, d_s, n, usable, d_out_a, d_out_s):
+        """pm_lookup_permute_device: P pairs of device columns (compressed
+        input A, compressed table S) of n rows -> A' at d_out_a[p], S' at
+        d_out_s[p], rows [0, usable); rows behind stay as they were.
+        d_out_a[p] may be d_a[p] and d_out_s[p] may be d_s[p]; an output may
+        alias nothing else.  Returns a (P, 2) u32 array of (status, row):
+        status 1 = an input value is absent from the table, row the smallest
+        first row of A' holding such a value."""
+        lists = [[int(p) for p in l] for l in (d_a, d_s, d_out_a, d_out_s)]
+        P = len(lists[0])
+        if any(len(l) != P for l in lists):
+            raise ValueError("one pointer per pair in each of the four lists")
+        if not 1 <= P <= LOOKUP_MAX_PAIRS:
+            raise ValueError("between 1 and 32767 pairs")
+        self._lookup_rows(n, usable)
+        if any(p == 0 for l in lists for p in l):
+            raise ValueError("null column pointer")
+        uses = {}
+        for role, l in enumerate(lists):
+            for p, ptr in enumerate(l):
+                uses.setdefault(ptr, []).append((p, role & 1, role >= 2))
+        for group in uses.values():
+            if any(out for _, _, out in group):
+                own = len(group) == 2 and group[0][:2] == group[1][:2] and group[0][2] != group[1][2]
+                if len(group) > 1 and not own:
+                    raise ValueError("an output column aliases a column other than its own input")
+        arrs = [(_vp * P)(*l) for l in lists]
+        status = np.zeros((P, 2), dtype=np.uint32)
+        _check(lib().pm_lookup_permute_device(self.h, curve, arrs[0], arrs[1], P, n, usable, arrs[2], arrs[3],
+                                              status.ctypes.data_as(_u32p)))
+        return status
+
+    def lookup_permute(self, curve, a, s, usable):
+        """pm_lookup_permute (halo2 permute_expression_pair): a, s (n, 4) u64
+        Montgomery -> (A', S', (status, row)); rows >= usable are those of a
+        and s.  Two PCIe crossings: parity, not speed."""
+        out_a, out_s = _as_u64(a, 4).copy(), _as_u64(s, 4).copy()
+        if out_a.shape != out_s.shape:
+            raise ValueError("a and s must have the same number of rows")
+        n = out_a.shape[0]
+        self._lookup_rows(n, usable)
+        status = np.zeros(2, dtype=np.uint32)
+        _check(lib().pm_lookup_permute(self.h, curve, _p(out_a), _p(out_s), n, usable, _p(out_a), _p(out_s),
+                                       status.ctypes.data_as(_u32p)))
+        return out_a, out_s, status
 
     # ---- extended-domain conversions (pm_coeff_to_extended* / pm_extended_to_coeff* /
     # pm_divide_by_vanishing_device / pm_fft_batch_device): d_in / d_out / d_data are

@@ -609,6 +609,68 @@ int pm_grand_product_device(pm_ctx* ctx, int curve, const void* const* d_cols, s
                             size_t S, const uint64_t omega[4], const uint64_t start[4], size_t active,
                             uint32_t flags, void* d_out_z /* S rows of n */, uint64_t* out_last /* S x 4, may be null */);
 
+/* ---- Lookup permuted columns ---------------------------------
+ * halo2 plonk/lookup/prover.rs::compress_expressions and
+ * permute_expression_pair [3P]: the step of create_proof between the advice
+ * commit and the lookup grand product, whose denominators read A' and S'
+ * (above).  Every scalar is 4 x u64 Montgomery and canonical, in and out.  The
+ * order is halo2's Ord on field elements: the numeric order of the canonical
+ * value, not the order of the Montgomery words.
+ *
+ * pm_lookup_compress_device: out[i] = sum_k theta^(m-1-k) col_k[i] (Horner
+ *   from zero: acc = acc * theta + col_k) over m >= 1 columns of n rows.
+ *   d_cols is a HOST array of m DEVICE pointers; theta is host memory.  With
+ *   m == 1 the output is the column and theta is not read (it may be NULL).
+ *   d_out may be one of the columns.
+ * pm_lookup_permute_device: P pairs (A, S) of compressed columns of n rows.
+ *   With usable <= n (halo2: n - (blinding_factors + 1)), per pair:
+ *     A'[0, usable) = A[0, usable) sorted ascending; T = the multiset
+ *     S[0, usable).  Row i is "first" when i == 0 or A'[i] != A'[i-1].  At a
+ *     first row S'[i] = A'[i], which uses up one instance of that value in T.
+ *     With L = T minus one instance per distinct value of A', ascending, and
+ *     r_0 < ... < r_{R-1} the rows that are not first, S'[r_{R-1-k}] = L[k].
+ *   Rows [usable, n) of both outputs are left exactly as the caller had them
+ *   (halo2 fills them with blinding values).  d_a, d_s, d_out_a, d_out_s are
+ *   HOST arrays of P DEVICE pointers.  d_out_a[p] may alias d_a[p] and
+ *   d_out_s[p] may alias d_s[p]; several pairs may read the same input column;
+ *   an output must not alias anything else of the call (another output, the
+ *   other input of its pair, any column of another pair).  n need not be a
+ *   power of two; usable may be anything in 1 .. n.
+ *   out_status (host memory, P x 2 words: status, row).  status 0: ok (row 0).
+ *   status 1: an input value is absent from the table (halo2:
+ *   Error::ConstraintSystemFailure); row is the smallest first row of A' whose
+ *   value T lacks, A' is still the sorted column and S' is unspecified.  The
+ *   call returns PM_OK either way: the status carries the circuit's failure,
+ *   and the other pairs of the call are unaffected.
+ *   All P pairs run in the same launches.  Any key distribution costs the
+ *   same: tiles of PM_LOOKUP_TILE keys are sorted in LDS and merged in
+ *   ceil(log2(usable / PM_LOOKUP_TILE)) passes, each merge block producing
+ *   PM_LOOKUP_MERGE keys.
+ * pm_lookup_permute: the host-pointer form of one pair (copy in, permute, copy
+ *   out): parity, not speed.  out_a may be a and out_s may be s; rows >= usable
+ *   of out_a / out_s are untouched.
+ *
+ * PM_ERR_ARG, all checked before the device is touched (the arguments before
+ * the context, so a binding can test them without a device): a null pointer
+ * (theta only when m > 1) or context, an unknown curve, n == 0, usable == 0 or
+ * usable > n, P == 0, m == 0, an output pointer equal to a pointer it may not
+ * alias.  PM_ERR_UNSUPPORTED: n > 2^28, P > PM_LOOKUP_MAX_PAIRS,
+ * m > PM_LOOKUP_MAX_COLS.  Context scratch (grow-only, sized for the whole call
+ * before the first launch is queued): 133 bytes per usable row per pair (two
+ * key buffers of 2 x 32, a row map and a flag), plus 8 bytes per 1024 rows. */
+#define PM_LOOKUP_MAX_PAIRS 32767      /* two columns per pair in one grid dimension */
+#define PM_LOOKUP_MAX_COLS  65535
+#define PM_LOOKUP_TILE  2048           /* keys sorted per block */
+#define PM_LOOKUP_MERGE 2048           /* keys produced per merge block */
+
+int pm_lookup_compress_device(pm_ctx* ctx, int curve, const void* const* d_cols /* host array of m device pointers */,
+                              size_t m, size_t n, const uint64_t theta[4], void* d_out);
+int pm_lookup_permute_device(pm_ctx* ctx, int curve, const void* const* d_a, const void* const* d_s, /* P pointers each */
+                             size_t P, size_t n, size_t usable,
+                             void* const* d_out_a, void* const* d_out_s, uint32_t* out_status /* P x 2: status,row */);
+int pm_lookup_permute(pm_ctx* ctx, int curve, const uint64_t* a, const uint64_t* s, size_t n, size_t usable,
+                      uint64_t* out_a, uint64_t* out_s, uint32_t out_status[2]);   /* host pointers: parity form */
+
 /* ---- Extended-domain conversions -----------------------------
  * halo2 `EvaluationDomain::{coeff_to_extended, extended_to_coeff,
  * divide_by_vanishing_poly}` [3P poly/domain.rs]: the transforms around the
