@@ -54,14 +54,17 @@ int transcript_launch(Ctx* ctx, const pm_proof_shape* s, size_t B, const uint64_
                       const void* d_scalars, void* d_ch, void* d_status, hipStream_t st, bool canon_ready = false,
                       uint32_t* dflags = nullptr);
 
-// Lanes per item for the latency-bound accumulator kernels: the largest
-// power of two 2^lg <= 2^maxlg that keeps items * 2^lg within about two
-// waves per SIMD of the 1024 on an MI355X.  Term additions: maxlg = 3 (8
-// lanes share a term's ~85 table additions; 16 measured no faster at B = 256,
-// the wider butterfly and the second wave per SIMD cost what the shorter loop
-// saves).
+// kAccLaneBudget, kAccSumLanes, kAccSlicedChains, the term plan (acc_terms) and the path choice
+// (acc_path): accum_plan.hpp
+// The two budgets as tests/accum_edge_util.py (engine_constants) reads them from this file's
+// text: the GPU edge tests place their batches by that path model, and it keeps reading them
+// where it always has.  The plan's own definitions are accum_plan.hpp's; the two cannot differ.
+namespace as_read_by_tests {
 constexpr size_t kAccLaneBudget = 1024 * 2 * 64;
 constexpr size_t kAccSumLanes = 16384;
+}  // namespace as_read_by_tests
+static_assert(as_read_by_tests::kAccLaneBudget == kAccLaneBudget && as_read_by_tests::kAccSumLanes == kAccSumLanes,
+              "accum_engine.hpp restates accum_plan.hpp's lane budgets");
 // 152 KiB (round 5, was 128): k_acc_scalars' per-proof rows grew with wave
 // 3's slot sums and the fold rows, and 32 proofs (config 5's rank slice)
 // should still fit one block
@@ -75,13 +78,6 @@ constexpr size_t kAccLadderFence = 40 * 1024;
 // (the quad ladder takes kAccSlicedFence, one block per CU, while its grid fits
 // the CUs: beside the twisted ladder's decode on the other stream its blocks
 // were otherwise packed two or three per CU, B = 256 ladder 0.27 -> 0.68 ms)
-// row-sliced ladder (k_acc_powers_s) up to this many chains: one wave each,
-// four per block and one block per CU (kAccSlicedFence), leaving CUs for the
-// side stream's transcript / k_acc_scalars blocks (which a ladder block on
-// every CU kept waiting until the ladder ended: B = 16 transcript 0.10 ->
-// 0.27 ms with 64-thread ladder blocks, profiles/r05/ladder_ab/r05_lad_scaling.jsonl
-// against r05_lad_b_auto.jsonl)
-constexpr size_t kAccSlicedChains = 800;
 constexpr size_t kAccSlicedFence = 84 * 1024;
 static_assert(2 * kAccSlicedFence > 160 * 1024 && kAccSlicedFence + kAccScalarsLds > 160 * 1024,
               "one sliced ladder block per CU, no side-stream block beside it");
@@ -89,75 +85,7 @@ static_assert(2 * kAccSlicedFence > 160 * 1024 && kAccSlicedFence + kAccScalarsL
 // (four per wave: 1024 waves)
 constexpr size_t kDecodeSlicedPoints = 4096;
 static_assert(kAccScalarsLds + kAccLadderFence > 160 * 1024, "the fence must not fit beside k_acc_scalars");
-inline uint32_t acc_auto_lanes(size_t items, uint32_t maxlg) {
-  uint32_t lg = 0;
-  while (lg < maxlg && (items << (lg + 1)) <= kAccLaneBudget) lg++;
-  return lg;
-}
-
-// The MSM term slots of one proof (accum_device_impl's plan): one slot per
-// distinct commitment of f in first-use order, then H's h_i, the W_j of w and
-// of zw, and g1 for e; qprog = (slot, eval) per query in set order.
-struct AccTerms {
-  std::vector<uint32_t> termsrc;  // (kind << 28) | idx ; VK index space: fixed, sigma, g1
-  std::vector<uint32_t> qprog;
-  uint32_t nslots = 0, h_slot0 = 0, T = 0, Tp = 0;  // Tp: proof-point terms (the powers-table chains)
-};
-inline void acc_terms(const pm_proof_shape* s, const AccLayout& L, const std::vector<std::vector<AccQuery>>& sets,
-                      AccTerms& t) {
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t> slot_of;
-  auto vk_index = [&](uint32_t kind, uint32_t idx) -> uint32_t {
-    return kind == kRefFixed ? idx : s->num_fixed_columns + idx;
-  };
-  for (auto& st : sets)
-    for (auto& x : st) {
-      uint32_t slot = kSlotH;
-      if (x.ref_kind != kRefH) {
-        auto key = std::make_pair(x.ref_kind, x.ref_idx);
-        auto it = slot_of.find(key);
-        if (it == slot_of.end()) {
-          slot = (uint32_t)t.termsrc.size();
-          slot_of[key] = slot;
-          t.termsrc.push_back(x.ref_kind == kRefProof ? x.ref_idx : ((1u << 28) | vk_index(x.ref_kind, x.ref_idx)));
-        } else {
-          slot = it->second;
-        }
-      }
-      t.qprog.push_back(slot);
-      t.qprog.push_back(x.eval);
-    }
-  t.h_slot0 = (uint32_t)t.termsrc.size();
-  for (uint32_t i = 0; i < s->quotient_degree; i++) t.termsrc.push_back(L.p_h + i);
-  t.nslots = (uint32_t)t.termsrc.size();
-  for (uint32_t j = 0; j < L.nsets; j++) t.termsrc.push_back(L.p_W + j);  // w
-  for (uint32_t j = 0; j < L.nsets; j++) t.termsrc.push_back(L.p_W + j);  // zw
-  t.termsrc.push_back((1u << 28) | (s->num_fixed_columns + s->n_perm_columns));  // e: g1
-  t.T = (uint32_t)t.termsrc.size();
-  t.Tp = 0;
-  for (uint32_t v : t.termsrc) t.Tp += (v >> 28) == 0 ? 1u : 0u;
-}
-
-// log2 of the lanes per term of the split (powers-table) form, 0 = the
-// one-lane GLV form.  The powers tables pay only while their chains stay
-// within ~3/4 of the lane budget: beyond it the 127-doubling chains share
-// SIMDs and queue, while the one-lane GLV products still run in one pass at
-// a flat ~1.16 ms.  Simple shape, T = 30 of which 21 proof points, wall per
-// batch (profiles/r02/vkt/): split 1.13 ms at B = 1024, 1.67 at 1536 against
-// one-lane 1.54 / 1.57 (the old rule without VK tables, 4 B T <= budget:
-// profiles/r02/xover/).
-inline uint32_t acc_split_lanes(const Ctx* ctx, size_t B, const AccTerms& t) {
-  const size_t nterm = B * t.T, nprf = B * t.Tp;
-  uint32_t lgS = ctx->acc_split >= 0 ? (uint32_t)ctx->acc_split
-                 : 4 * (nprf << 2) > 3 * kAccLaneBudget ? 0u
-                                                        : acc_auto_lanes(nterm, 3);
-  // 16 / 32 lanes per term only while the term additions still fit one wave
-  // per SIMD (B = 16: k_acc_termadd 0.075 ms at 16 lanes, 0.061 at 32; B = 256
-  // stays at 8 lanes: 0.129 ms, 16 lanes 0.138, 32 lanes 0.197:
-  // profiles/r02/pow/timing_pow1.jsonl)
-  if (ctx->acc_split < 0 && lgS == 3)
-    while (lgS < 5 && (nterm << (lgS + 1)) <= kAccLaneBudget / 2) lgS++;
-  return lgS;
-}
+static_assert(kAccNoPair == kAccNoByte, "a pair's missing term is the kernels' kAccNoByte");
 
 // static LDS of a decode instantiation (the fence is the block's total)
 template <class Cv, bool SLICED>
@@ -198,24 +126,22 @@ constexpr size_t kDecodePairFence = 80 * 1024;
 static_assert(2 * kDecodePairFence <= 160 * 1024 && kDecodePairFence + kAccSlicedFence > 160 * 1024,
               "decode pair fence");
 
-// vk_repr != nullptr: the challenges are first replayed into d_ch on the
-// device (transcript_device_impl); the split ladder then runs concurrently
-// with the replay and k_acc_scalars on the reduction stream.
+// What accum_device_impl uploads and launches with, built on the host from the
+// validated shape: the header, the program words (expression code, query and
+// term tables, the two-term lanes' pairs), the constants (Montgomery) and the
+// VK points, and k_acc_scalars' LDS rows.
+struct AccProgram {
+  AccumHdr h;
+  std::vector<uint32_t> prog, cst;
+  std::vector<uint64_t> vk;
+  AccTerms tm;
+  uint32_t p_pairs = 0;
+  size_t row_bytes = 0, tail_bytes = 0;
+};
 template <class Cv>
-int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d_points, const void* d_scalars,
-                      void* d_ch, void* d_out, void* d_hout, const uint64_t* vk_repr, void* d_status,
-                      bool canon_ready = false, uint32_t* dflags = nullptr, const AccDecode* dec = nullptr) {
-  using F = typename Cv::Base;
+int accum_build(const pm_proof_shape* s, size_t B, const std::vector<AccQuery>& q, const AccLayout& L,
+                const AccDecode* dec, AccProgram& out) {
   using Fs = typename Cv::Scalar;
-  const auto tplan = std::chrono::steady_clock::now();  // host planning (stat "accum_plan_host")
-  std::vector<AccQuery> q;
-  AccLayout L;
-  const std::string err = acc_validate(s, q, L, nullptr);
-  if (!err.empty()) return set_error(PM_ERR_ARG, "accum shape: " + err);
-  if (B == 0) return PM_OK;
-  if (B > (1u << 20)) return set_error(PM_ERR_UNSUPPORTED, "accum batch larger than 2^20 proofs");
-  if (vk_repr && !d_ch) return set_error(PM_ERR_ARG, "null challenge buffer");
-
   std::vector<int32_t> rots;
   std::vector<std::vector<AccQuery>> sets;
   acc_group_sets(q, rots, sets);
@@ -223,14 +149,14 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
     if (st.size() > kAccMaxPerSet) return set_error(PM_ERR_UNSUPPORTED, "accum: rotation set too large");
 
   // --- term slots (acc_terms)
-  AccTerms tm;
+  AccTerms& tm = out.tm;
   acc_terms(s, L, sets, tm);
   const std::vector<uint32_t>& termsrc = tm.termsrc;
   const std::vector<uint32_t>& qprog = tm.qprog;
   const uint32_t h_slot0 = tm.h_slot0, nslots = tm.nslots, T = tm.T;
 
   // --- program words
-  AccumHdr h{};
+  AccumHdr& h = out.h;
   h.B = (uint32_t)B;
   h.npts = L.npts;
   h.nsc = L.nsc;
@@ -252,7 +178,7 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   h.sc_lk = L.s_lk;
   h.h_slot0 = h_slot0;
   h.nh = s->quotient_degree;
-  std::vector<uint32_t> prog;
+  std::vector<uint32_t>& prog = out.prog;
   auto put = [&](const uint32_t* p, uint32_t n, uint32_t& off, uint32_t& len) {
     off = (uint32_t)prog.size();
     len = n;
@@ -294,22 +220,11 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   }
 
   // pairs of terms of one output for the one-lane form's two-term lanes
-  // (k_acc_termmul NT = 2), per output range as k_acc_sum folds them
-  const uint32_t p_pairs = (uint32_t)prog.size();
-  uint32_t npair = 0;
-  {
-    const uint32_t T0 = (uint32_t)termsrc.size(), ns = nslots, nst = L.nsets;
-    const uint32_t lo[4] = {0, ns, ns + nst, T0 - 1}, hi[4] = {ns, ns + nst, ns + 2 * nst, T0};
-    for (int o = 0; o < 4; o++)
-      for (uint32_t t = lo[o]; t < hi[o]; t += 2) {
-        prog.push_back(t);
-        prog.push_back(t + 1 < hi[o] ? t + 1 : kAccNoByte);
-        npair++;
-      }
-  }
+  out.p_pairs = (uint32_t)prog.size();
+  prog.insert(prog.end(), tm.pairs.begin(), tm.pairs.end());
 
   // --- constants (Montgomery)
-  std::vector<uint32_t> cst;
+  std::vector<uint32_t>& cst = out.cst;
   h.c_user = 0;
   for (uint32_t i = 0; i < s->n_constants; i++) push_fe<Fs>(cst, fe_from_u64<Fs>(s->constants + 4 * i));
   const Fe<Fs> omega = fe_from_u64<Fs>(s->omega), delta = fe_from_u64<Fs>(s->delta);
@@ -353,7 +268,7 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   h.c_n29 = (uint32_t)(cst.size() / 8);
   push_fe<Fs>(cst, r261(nmont));
   // --- VK points: fixed commitments, sigma commitments, g1
-  std::vector<uint64_t> vk;
+  std::vector<uint64_t>& vk = out.vk;
   for (uint32_t i = 0; i < s->num_fixed_columns; i++) vk.insert(vk.end(), s->fixed_commitments + 8 * i, s->fixed_commitments + 8 * i + 8);
   for (uint32_t i = 0; i < s->n_perm_columns; i++) vk.insert(vk.end(), s->sigma_commitments + 8 * i, s->sigma_commitments + 8 * i + 8);
   vk.insert(vk.end(), s->g1, s->g1 + 8);
@@ -363,29 +278,72 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   // rows do not fit is refused here, before anything is uploaded or launched
   // (the check used to sit behind the ladder's launch, so the error returned
   // with that kernel in flight and the VK tables invalidated)
-  const size_t row_bytes =
+  out.row_bytes =
       (size_t)(L.nsc + T + kAccXVals + acc_num_vals(h) + 2 * (h.bf + 3) + kAccStack + h.nslots + h.nh) * 32;
-  const size_t tail_bytes = (size_t)acc_scalars_tail_words(h) * 4;
-  if (tail_bytes + 2 * row_bytes > kAccScalarsLds)
+  out.tail_bytes = (size_t)acc_scalars_tail_words(h) * 4;
+  if (out.tail_bytes + 2 * out.row_bytes > kAccScalarsLds)
     return set_error(PM_ERR_UNSUPPORTED, "accum: too many evaluations / terms per proof");
 
+  return PM_OK;
+}
+
+// vk_repr != nullptr: the challenges are first replayed into d_ch on the
+// device (transcript_device_impl); the split ladder then runs concurrently
+// with the replay and k_acc_scalars on the reduction stream.
+template <class Cv>
+int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d_points, const void* d_scalars,
+                      void* d_ch, void* d_out, void* d_hout, const uint64_t* vk_repr, void* d_status,
+                      bool canon_ready = false, uint32_t* dflags = nullptr, const AccDecode* dec = nullptr) {
+  using F = typename Cv::Base;
+  using Fs = typename Cv::Scalar;
+  const auto tplan = std::chrono::steady_clock::now();  // host planning (stat "accum_plan_host")
+  std::vector<AccQuery> q;
+  AccLayout L;
+  const std::string err = acc_validate(s, q, L, nullptr);
+  if (!err.empty()) return set_error(PM_ERR_ARG, "accum shape: " + err);
+  if (B == 0) return PM_OK;
+  if (B > (1u << 20)) return set_error(PM_ERR_UNSUPPORTED, "accum batch larger than 2^20 proofs");
+  if (vk_repr && !d_ch) return set_error(PM_ERR_ARG, "null challenge buffer");
+
+  AccProgram ap;
+  if (int brc = accum_build<Cv>(s, B, q, L, dec, ap)) return brc;
+  AccumHdr& h = ap.h;
+  const uint32_t T = ap.tm.T;
   const hipStream_t st = ctx->stream;
   int rc;
-  if ((rc = ctx->acc_prog.put(prog, st))) return rc;
-  if ((rc = ctx->acc_const.put(cst, st, 32))) return rc;
-  if ((rc = ctx->acc_vk.put(vk, st))) return rc;
+  if ((rc = ctx->acc_prog.put(ap.prog, st))) return rc;
+  if ((rc = ctx->acc_const.put(ap.cst, st, 32))) return rc;
+  if ((rc = ctx->acc_vk.put(ap.vk, st))) return rc;
   if ((rc = ctx->acc_coef.ensure((size_t)B * T * 32))) return rc;
   if ((rc = ctx->acc_part.ensure((size_t)B * T * sizeof(Xyzz<F>)))) return rc;
   const uint32_t* dprog = (const uint32_t*)ctx->acc_prog.buf.p;
   uint32_t* dcoef = (uint32_t*)ctx->acc_coef.p;
   Xyzz<F>* dpart = (Xyzz<F>*)ctx->acc_part.p;
   const size_t nterm = (size_t)B * T, nprf = (size_t)B * h.Tp;
-  const uint32_t lgS = acc_split_lanes(ctx, B, tm);
-  // few terms (B <= ~34 for the simple shape): 16 quads per term with
-  // quad-cooperative additions (k_acc_termadd<Cv, true>)
-  const bool quad_terms = ctx->acc_split < 0 && lgS == 5 && nterm * 64 <= kAccLaneBudget / 2;
-  const uint32_t lgT = quad_terms ? 4u : lgS;  // log2 of lanes (or quads) per term
-  const uint32_t S = 1u << lgS;
+  // the split form's tables, and which of the per-VK ones this call builds:
+  // rebuilt (in the same launch, beside the proofs' chains) only when the
+  // curve or the VK points differ from the last build, or the buffer was
+  // reallocated
+  const size_t nvk = ap.vk.size() / 8;
+  std::vector<uint64_t> key;
+  bool vk_current = false;
+  if (acc_split_lanes(ctx->acc_split, B, T, h.Tp) > 0) {
+    const size_t tab = (size_t)kPowPos * kPowPoint * sizeof(uint4);
+    if ((rc = ctx->acc_lad.ensure(std::max<size_t>(nprf, 1) * tab))) return rc;
+    if ((rc = ctx->acc_vkpow.ensure(std::max<size_t>(nvk, 1) * tab))) return rc;
+    key = ap.vk;
+    key.push_back((uint64_t)F::MOD[1] << 32 | F::MOD[2]);  // the curve (its base field)
+    vk_current = ctx->acc_vkpow_gen == ctx->acc_vkpow.gen && ctx->acc_vkpow_key == key;
+  }
+  const uint32_t nvk_build = vk_current ? 0u : (uint32_t)nvk;
+  // the kernels' forms (accum_plan.hpp acc_path)
+  AccPathIn pin;
+  pin.B = B, pin.T = T, pin.Tp = h.Tp, pin.npair = ap.tm.npair;
+  pin.split = ctx->acc_split, pin.tpl = ctx->acc_tpl, pin.ladder = ctx->acc_ladder;
+  pin.nvk_build = nvk_build;
+  pin.row_bytes = ap.row_bytes, pin.tail_bytes = ap.tail_bytes, pin.lds_cap = kAccScalarsLds;
+  const AccPath path = acc_path(pin);
+  const uint32_t lgS = path.lgS, S = 1u << lgS;
   // Streams: with the split ladder (points only, the critical chain) it goes
   // first on the main stream, and the transcript replay + k_acc_scalars run
   // beside it on the reduction stream (kept off the ladder's CUs by the LDS
@@ -402,20 +360,9 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   if (h.twist && !dec->launched && (rc = ctx->acc_corr.ensure((size_t)B * L.npts * kAccCorrWords * sizeof(uint4))))
     return rc;
   std::vector<uint64_t> built_key;  // VK tables built by this call (committed after its final sync)
-  bool lad_sliced = false;          // the ladder's chain form (below)
   // without the twist the decode comes first: everything after reads its points
   if (dec && !dec->launched && !h.twist && (rc = dec->launch(st, kDecodeFence, nullptr))) return rc;
   if (lgS > 0) {  // inputs and uploads are ready at this point of the stream
-    const size_t tab = (size_t)kPowPos * kPowPoint * sizeof(uint4), nvk = vk.size() / 8;
-    if ((rc = ctx->acc_lad.ensure(std::max<size_t>(nprf, 1) * tab))) return rc;
-    if ((rc = ctx->acc_vkpow.ensure(std::max<size_t>(nvk, 1) * tab))) return rc;
-    // per-VK tables: rebuilt (in the same launch, beside the proofs' chains)
-    // only when the curve or the VK points differ from the last build, or
-    // the buffer was reallocated
-    std::vector<uint64_t> key(vk);
-    key.push_back((uint64_t)F::MOD[1] << 32 | F::MOD[2]);  // the curve (its base field)
-    const bool vk_current = ctx->acc_vkpow_gen == ctx->acc_vkpow.gen && ctx->acc_vkpow_key == key;
-    const uint32_t nvk_build = vk_current ? 0u : (uint32_t)nvk;
     // up: the inputs and uploads (programs, constants, the decoder's map)
     // are complete; the other stream starts from it
     up = ctx->next_event();
@@ -436,17 +383,13 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
     if (h.twist) HIP_TRY(hipStreamWaitEvent(lst, up, 0));
     const uint32_t* lproofs = h.twist ? (const uint32_t*)dec->proofs : nullptr;
     const uint32_t* linst = h.twist ? (const uint32_t*)dec->inst : nullptr;
-    // few chains: one row-sliced wave per chain (slice29.hpp, ~2x shorter
-    // steps while the waves fit one per SIMD); more: a quad per chain
     const size_t chains = nprf + nvk_build;
-    const bool sliced = ctx->acc_ladder >= 0 ? ctx->acc_ladder == 1 : chains <= kAccSlicedChains;
-    lad_sliced = sliced;
     if (ctx->timing) {  // entry -> the ladder's launch (filter "accum_host": no kernel events)
       auto& stt = ctx->stats["accum_plan_host"];
       stt.first += 1;
       stt.second += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tplan).count();
     }
-    if (chains > 0 && sliced)
+    if (chains > 0 && path.sliced)
       PM_LAUNCH_ST(ctx, lst, "acc_ladder",
                 (k_acc_powers_s<Cv><<<(unsigned)((chains + 3) / 4), 256, kAccSlicedFence, lst>>>(
                     h, dprog, (const uint32_t*)d_points, lproofs, linst, (const uint32_t*)ctx->acc_vk.buf.p, nvk_build,
@@ -475,17 +418,12 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   // status: the replay stores bits 0-1 per proof, k_acc_scalars ORs in the
   // denominator bit; without a replay the words start at zero
   if (d_status && !vk_repr) HIP_TRY(hipMemsetAsync(d_status, 0, B * sizeof(uint32_t), side));
-  // k_acc_scalars: 4 waves per block of np proofs (row_bytes / tail_bytes
-  // above, checked against kAccScalarsLds before the first launch)
-  // 16 proofs per block (round 5): wave 0 then runs the Lagrange chain with a
-  // quad per proof (acc_lagrange_q, ~half the one-lane chain); more blocks
-  // only spread the batch over more CUs
-  const uint32_t np = (uint32_t)std::min<size_t>(16, (kAccScalarsLds - tail_bytes) / row_bytes - 1);
-  const size_t lds = std::max(row_bytes * (np + 1) + tail_bytes, lgS > 0 ? kAccScalarsLds : 0);
+  // k_acc_scalars: 4 waves per block of np proofs (acc_path)
+  const size_t lds = path.lds;
   PM_LAUNCH_ST(ctx, side, "acc_scalars",
-               (k_acc_scalars<Fs><<<(unsigned)((B + np - 1) / np), 256, lds, side>>>(
+               (k_acc_scalars<Fs><<<(unsigned)((B + path.np - 1) / path.np), 256, lds, side>>>(
                    h, dprog, (const uint32_t*)ctx->acc_const.buf.p, (const uint32_t*)d_scalars, (const uint32_t*)d_ch,
-                   dcoef, (uint32_t*)d_hout, np, (uint32_t*)d_status)));
+                   dcoef, (uint32_t*)d_hout, path.np, (uint32_t*)d_status)));
   // the stream of the term additions and sums (tst): the one whose chain
   // ends last, so the cross-stream wait finds its event already signalled.
   // With the twist and the quad ladder (0.26 ms against decode -> transcript
@@ -494,64 +432,44 @@ int accum_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* d
   // (profiles/r05/tail_ab/, interleaved runs: B = 64 0.433 -> 0.427 ms, B =
   // 128 0.454 -> 0.446; B = 16 0.341 -> 0.347 had it followed the ladder too)
   const bool tail_red = ctx->acc_tail != 0;  // PM_ACC_OPT_TAIL_STREAM = 0: always the main stream
-  const hipStream_t tst = lgS > 0 && h.twist && !lad_sliced && tail_red ? ctx->red_stream : st;
-  uint32_t pstep = 1;  // k_acc_sum's row step (2 after two-term lanes)
+  const hipStream_t tst = lgS > 0 && h.twist && !path.sliced && tail_red ? ctx->red_stream : st;
   if (lgS > 0) {
     // the term additions wait for the other stream: the scalar block (side),
     // or with the twist the ladder (or, on the ladder's stream, the scalar block)
     HIP_TRY(hipEventRecord(sc_done, h.twist ? (tst == st ? ctx->red_stream : st) : side));
     HIP_TRY(hipStreamWaitEvent(tst, sc_done, 0));
-    if (quad_terms)
+    if (path.quad_terms)
       PM_LAUNCH_ST(ctx, tst, "acc_termmul",
                 (k_acc_termadd<Cv, true><<<(unsigned)((nterm * 64 + 255) / 256), 256, 0, tst>>>(
                     h, dprog, dcoef, (const uint4*)ctx->acc_lad.p, (const uint4*)ctx->acc_vkpow.p,
-                    (const uint4*)ctx->acc_corr.p, lgT, dpart)));
+                    (const uint4*)ctx->acc_corr.p, path.lgT, dpart)));
     else
       PM_LAUNCH_ST(ctx, tst, "acc_termmul",
                 (k_acc_termadd<Cv><<<(unsigned)((nterm * S + 255) / 256), 256, 0, tst>>>(
                     h, dprog, dcoef, (const uint4*)ctx->acc_lad.p, (const uint4*)ctx->acc_vkpow.p,
                     (const uint4*)ctx->acc_corr.p, lgS, dpart)));
   } else {
-    // GLV products by signed 3-bit windows; two terms of one output per lane
-    // (shared doublings) once one term per lane would put more than one wave
-    // on a SIMD, while the pairs still fit one wave per SIMD (their 144 KiB of
-    // LDS tables per block keep one block per CU); PM_ACC_OPT_TERMS_PER_LANE
-    // forces 1 or 2
-    const bool pairs_fit = (size_t)B * npair <= kAccLaneBudget / 2;
-    const int tpl = ctx->acc_tpl > 0 ? ctx->acc_tpl : (nterm > kAccLaneBudget / 2 && pairs_fit ? 2 : 1);
+    // GLV products by signed 3-bit windows, one or two terms of one output per lane (acc_path)
     const uint32_t* dvk = (const uint32_t*)ctx->acc_vk.buf.p;
-    if (tpl == 2) pstep = 2;
-    if (tpl == 2)
+    if (path.tpl == 2)
       PM_LAUNCH(ctx, "acc_termmul",
-                (k_acc_termmul<Cv, 2><<<(unsigned)(((size_t)B * npair + 255) / 256), 256, 0, st>>>(
-                    h, dprog, dcoef, (const uint32_t*)d_points, dvk, p_pairs, npair, dpart)));
+                (k_acc_termmul<Cv, 2><<<(unsigned)(((size_t)B * ap.tm.npair + 255) / 256), 256, 0, st>>>(
+                    h, dprog, dcoef, (const uint32_t*)d_points, dvk, ap.p_pairs, ap.tm.npair, dpart)));
     else
       PM_LAUNCH(ctx, "acc_termmul",
                 (k_acc_termmul<Cv, 1><<<(unsigned)((nterm + 255) / 256), 256, 0, st>>>(
                     h, dprog, dcoef, (const uint32_t*)d_points, dvk, 0u, 0u, dpart)));
   }
-  // lanes per output: at most ~16 K in total.  The affine conversion runs on
-  // lane 0 of each group, and it slowed from ~0.08 to ~0.14 ms when 32
-  // lanes per output spread the 1024 outputs of B = 256 over 512 waves
-  // (profiles/r01_s4/accum_sum_lanes.jsonl).
-  uint32_t lgL = 0;
-  while (lgL < 5 && ((size_t)B * 4 << (lgL + 1)) <= kAccSumLanes) lgL++;
-  // large batches: still quads (quad-cooperative additions and inversion),
-  // up to two per output, within one wave per SIMD; one lane per output ran
-  // f's ~12 term sums and a lone-lane inversion while the w / zw / e lanes of
-  // its wave idled (round 6, profiles/r06/sum_lanes_ab.jsonl: B = 4096 0.133
-  // -> 0.114 ms, 3072 0.133 -> 0.080)
-  while (lgL < 3 && ((size_t)B * 4 << (lgL + 1)) <= kAccLaneBudget / 2) lgL++;
-  {
+  {  // k_acc_sum: 2^lgL lanes per output (acc_path)
     hipEvent_t done = ctx->next_event();
     if (!done) return set_error(PM_ERR_HIP, "hipEventCreate failed");
-    const unsigned nblk = (unsigned)((B * 4 * (1u << lgL) + 63) / 64);
+    const unsigned nblk = (unsigned)((B * 4 * (1u << path.lgL) + 63) / 64);
     if (ctx->timing) {
-      PM_LAUNCH_ST(ctx, tst, "acc_sum", (k_acc_sum<Cv><<<nblk, 64, 0, tst>>>(h, dpart, lgL, (uint32_t*)d_out, pstep)));
+      PM_LAUNCH_ST(ctx, tst, "acc_sum", (k_acc_sum<Cv><<<nblk, 64, 0, tst>>>(h, dpart, path.lgL, (uint32_t*)d_out, path.pstep)));
       HIP_TRY(hipEventRecord(done, tst));
     } else {  // the completion event rides on the dispatch (no marker packet behind it)
-      hipExtLaunchKernelGGL(k_acc_sum<Cv>, dim3(nblk), dim3(64), 0, tst, nullptr, done, 0, h, dpart, lgL,
-                            (uint32_t*)d_out, pstep);
+      hipExtLaunchKernelGGL(k_acc_sum<Cv>, dim3(nblk), dim3(64), 0, tst, nullptr, done, 0, h, dpart, path.lgL,
+                            (uint32_t*)d_out, path.pstep);
       HIP_TRY(hipGetLastError());
     }
     if (int rc = wait_event(ctx, done)) return rc;
@@ -798,7 +716,7 @@ int proofs_device_impl(Ctx* ctx, const pm_proof_shape* s, size_t B, const void* 
     acc_group_sets(q, rots, sets);
     AccTerms tm;
     acc_terms(s, L, sets, tm);
-    const bool split = vk_repr && acc_split_lanes(ctx, B, tm) > 0;
+    const bool split = vk_repr && acc_split_lanes(ctx->acc_split, B, tm.T, tm.Tp) > 0;
     const size_t nprf = B * (size_t)tm.Tp;
     lad_blocks = nprf <= kAccSlicedChains ? (nprf + 3) / 4 : (4 * nprf + 255) / 256;
     twist = split && ctx->acc_twist != 0;

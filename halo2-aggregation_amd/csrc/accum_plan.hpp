@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pasta_msm.h"
@@ -214,6 +215,183 @@ inline std::string acc_validate(const pm_proof_shape* s, std::vector<AccQuery>& 
   if (ng + L.n_perm_sets + 5 * s->num_lookups == 0) return "no expressions (vanishing.rs:147 asserts >= 1)";
   if (ngates) *ngates = ng;
   return "";
+}
+
+// ------------------------------------------------------------ path choice
+// Lanes per item for the latency-bound accumulator kernels: the largest
+// power of two 2^lg <= 2^maxlg that keeps items * 2^lg within about two
+// waves per SIMD of the 1024 on an MI355X.  Term additions: maxlg = 3 (8
+// lanes share a term's ~85 table additions; 16 measured no faster at B = 256,
+// the wider butterfly and the second wave per SIMD cost what the shorter loop
+// saves).
+constexpr size_t kAccLaneBudget = 1024 * 2 * 64;
+constexpr size_t kAccSumLanes = 16384;
+// row-sliced ladder (k_acc_powers_s) up to this many chains: one wave each,
+// four per block and one block per CU (kAccSlicedFence), leaving CUs for the
+// side stream's transcript / k_acc_scalars blocks (which a ladder block on
+// every CU kept waiting until the ladder ended: B = 16 transcript 0.10 ->
+// 0.27 ms with 64-thread ladder blocks, profiles/r05/ladder_ab/r05_lad_scaling.jsonl
+// against r05_lad_b_auto.jsonl)
+constexpr size_t kAccSlicedChains = 800;
+inline uint32_t acc_auto_lanes(size_t items, uint32_t maxlg) {
+  uint32_t lg = 0;
+  while (lg < maxlg && (items << (lg + 1)) <= kAccLaneBudget) lg++;
+  return lg;
+}
+
+// The MSM term slots of one proof (accum_device_impl's plan): one slot per
+// distinct commitment of f in first-use order, then H's h_i, the W_j of w and
+// of zw, and g1 for e; qprog = (slot, eval) per query in set order.
+constexpr uint32_t kAccNoPair = 0xffffffffu;  // a pair's missing second term
+struct AccTerms {
+  std::vector<uint32_t> termsrc;  // (kind << 28) | idx ; VK index space: fixed, sigma, g1
+  std::vector<uint32_t> qprog;
+  uint32_t nslots = 0, h_slot0 = 0, T = 0, Tp = 0;  // Tp: proof-point terms (the powers-table chains)
+  // pairs of terms of one output for the one-lane form's two-term lanes
+  // (k_acc_termmul NT = 2), per output range as k_acc_sum folds them
+  std::vector<uint32_t> pairs;  // (t, t + 1 or kAccNoPair) per pair
+  uint32_t npair = 0;
+};
+inline void acc_terms(const pm_proof_shape* s, const AccLayout& L, const std::vector<std::vector<AccQuery>>& sets,
+                      AccTerms& t) {
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> slot_of;
+  auto vk_index = [&](uint32_t kind, uint32_t idx) -> uint32_t {
+    return kind == kRefFixed ? idx : s->num_fixed_columns + idx;
+  };
+  for (auto& st : sets)
+    for (auto& x : st) {
+      uint32_t slot = kSlotH;
+      if (x.ref_kind != kRefH) {
+        auto key = std::make_pair(x.ref_kind, x.ref_idx);
+        auto it = slot_of.find(key);
+        if (it == slot_of.end()) {
+          slot = (uint32_t)t.termsrc.size();
+          slot_of[key] = slot;
+          t.termsrc.push_back(x.ref_kind == kRefProof ? x.ref_idx : ((1u << 28) | vk_index(x.ref_kind, x.ref_idx)));
+        } else {
+          slot = it->second;
+        }
+      }
+      t.qprog.push_back(slot);
+      t.qprog.push_back(x.eval);
+    }
+  t.h_slot0 = (uint32_t)t.termsrc.size();
+  for (uint32_t i = 0; i < s->quotient_degree; i++) t.termsrc.push_back(L.p_h + i);
+  t.nslots = (uint32_t)t.termsrc.size();
+  for (uint32_t j = 0; j < L.nsets; j++) t.termsrc.push_back(L.p_W + j);  // w
+  for (uint32_t j = 0; j < L.nsets; j++) t.termsrc.push_back(L.p_W + j);  // zw
+  t.termsrc.push_back((1u << 28) | (s->num_fixed_columns + s->n_perm_columns));  // e: g1
+  t.T = (uint32_t)t.termsrc.size();
+  t.Tp = 0;
+  for (uint32_t v : t.termsrc) t.Tp += (v >> 28) == 0 ? 1u : 0u;
+  t.pairs.clear();
+  t.npair = 0;
+  {
+    const uint32_t T0 = (uint32_t)t.termsrc.size(), ns = t.nslots, nst = L.nsets;
+    const uint32_t lo[4] = {0, ns, ns + nst, T0 - 1}, hi[4] = {ns, ns + nst, ns + 2 * nst, T0};
+    for (int o = 0; o < 4; o++)
+      for (uint32_t k = lo[o]; k < hi[o]; k += 2) {
+        t.pairs.push_back(k);
+        t.pairs.push_back(k + 1 < hi[o] ? k + 1 : kAccNoPair);
+        t.npair++;
+      }
+  }
+}
+
+// log2 of the lanes per term of the split (powers-table) form, 0 = the
+// one-lane GLV form.  The powers tables pay only while their chains stay
+// within ~3/4 of the lane budget: beyond it the 127-doubling chains share
+// SIMDs and queue, while the one-lane GLV products still run in one pass at
+// a flat ~1.16 ms.  Simple shape, T = 30 of which 21 proof points, wall per
+// batch (profiles/r02/vkt/): split 1.13 ms at B = 1024, 1.67 at 1536 against
+// one-lane 1.54 / 1.57 (the old rule without VK tables, 4 B T <= budget:
+// profiles/r02/xover/).
+// split: pm_ctx_set_accum_split (-1 = auto)
+inline uint32_t acc_split_lanes(int split, size_t B, uint32_t T, uint32_t Tp) {
+  const size_t nterm = B * T, nprf = B * Tp;
+  uint32_t lgS = split >= 0 ? (uint32_t)split
+                 : 4 * (nprf << 2) > 3 * kAccLaneBudget ? 0u
+                                                        : acc_auto_lanes(nterm, 3);
+  // 16 / 32 lanes per term only while the term additions still fit one wave
+  // per SIMD (B = 16: k_acc_termadd 0.075 ms at 16 lanes, 0.061 at 32; B = 256
+  // stays at 8 lanes: 0.129 ms, 16 lanes 0.138, 32 lanes 0.197:
+  // profiles/r02/pow/timing_pow1.jsonl)
+  if (split < 0 && lgS == 3)
+    while (lgS < 5 && (nterm << (lgS + 1)) <= kAccLaneBudget / 2) lgS++;
+  return lgS;
+}
+
+// The kernels' forms for a batch of B proofs of T terms (Tp of them proof
+// points, npair two-term lanes).  The context's options come as plain ints,
+// -1 = auto: split (pm_ctx_set_accum_split), tpl (PM_ACC_OPT_TERMS_PER_LANE),
+// ladder (pm_ctx_set_accum_ladder: 0 quads, 1 row-sliced waves).
+struct AccPathIn {
+  size_t B;
+  uint32_t T, Tp, npair;
+  int split = -1, tpl = -1, ladder = -1;
+  size_t nvk_build = 0;  // VK points whose powers tables this call builds beside the proofs' chains
+  // k_acc_scalars: bytes of a proof's rows and of the tail (constants +
+  // program), and the block's LDS cap; row_bytes = 0: np and lds are not asked
+  size_t row_bytes = 0, tail_bytes = 0, lds_cap = 0;
+};
+struct AccPath {
+  uint32_t lgS;     // log2 lanes per term of the split form, 0 = the one-lane GLV form
+  bool quad_terms;  // k_acc_termadd<Cv, true>
+  uint32_t lgT;     // log2 of lanes (or quads) per term
+  int tpl;          // the one-lane form's terms per lane (0 in the split form)
+  uint32_t pstep;   // k_acc_sum's row step (2 after two-term lanes)
+  uint32_t lgL;     // log2 lanes per output of k_acc_sum
+  bool sliced;      // the split form's ladder: row-sliced waves (else a quad per chain)
+  uint32_t np;      // k_acc_scalars: proofs per block
+  size_t lds;       // ... and its LDS request (the whole cap beside a split ladder: the fence)
+};
+inline AccPath acc_path(const AccPathIn& in) {
+  AccPath p{};
+  const size_t B = in.B, nterm = B * in.T, nprf = B * in.Tp;
+  p.lgS = acc_split_lanes(in.split, B, in.T, in.Tp);
+  // few terms (B <= ~34 for the simple shape): 16 quads per term with
+  // quad-cooperative additions (k_acc_termadd<Cv, true>)
+  p.quad_terms = in.split < 0 && p.lgS == 5 && nterm * 64 <= kAccLaneBudget / 2;
+  p.lgT = p.quad_terms ? 4u : p.lgS;  // log2 of lanes (or quads) per term
+  p.pstep = 1;
+  if (p.lgS > 0) {
+    // few chains: one row-sliced wave per chain (slice29.hpp, ~2x shorter
+    // steps while the waves fit one per SIMD); more: a quad per chain
+    const size_t chains = nprf + in.nvk_build;
+    p.sliced = in.ladder >= 0 ? in.ladder == 1 : chains <= kAccSlicedChains;
+  } else {
+    // GLV products by signed 3-bit windows; two terms of one output per lane
+    // (shared doublings) once one term per lane would put more than one wave
+    // on a SIMD, while the pairs still fit one wave per SIMD (their 144 KiB of
+    // LDS tables per block keep one block per CU); PM_ACC_OPT_TERMS_PER_LANE
+    // forces 1 or 2
+    const bool pairs_fit = (size_t)B * in.npair <= kAccLaneBudget / 2;
+    p.tpl = in.tpl > 0 ? in.tpl : (nterm > kAccLaneBudget / 2 && pairs_fit ? 2 : 1);
+    if (p.tpl == 2) p.pstep = 2;
+  }
+  // lanes per output: at most ~16 K in total.  The affine conversion runs on
+  // lane 0 of each group, and it slowed from ~0.08 to ~0.14 ms when 32
+  // lanes per output spread the 1024 outputs of B = 256 over 512 waves
+  // (profiles/r01_s4/accum_sum_lanes.jsonl).
+  uint32_t lgL = 0;
+  while (lgL < 5 && ((size_t)B * 4 << (lgL + 1)) <= kAccSumLanes) lgL++;
+  // large batches: still quads (quad-cooperative additions and inversion),
+  // up to two per output, within one wave per SIMD; one lane per output ran
+  // f's ~12 term sums and a lone-lane inversion while the w / zw / e lanes of
+  // its wave idled (round 6, profiles/r06/sum_lanes_ab.jsonl: B = 4096 0.133
+  // -> 0.114 ms, 3072 0.133 -> 0.080)
+  while (lgL < 3 && ((size_t)B * 4 << (lgL + 1)) <= kAccLaneBudget / 2) lgL++;
+  p.lgL = lgL;
+  if (in.row_bytes) {
+    // k_acc_scalars: 4 waves per block of np proofs (row_bytes / tail_bytes
+    // above, checked against kAccScalarsLds before the first launch)
+    // 16 proofs per block (round 5): wave 0 then runs the Lagrange chain with a
+    // quad per proof (acc_lagrange_q, ~half the one-lane chain); more blocks
+    // only spread the batch over more CUs
+    p.np = (uint32_t)std::min<size_t>(16, (in.lds_cap - in.tail_bytes) / in.row_bytes - 1);
+    p.lds = std::max(in.row_bytes * (p.np + 1) + in.tail_bytes, p.lgS > 0 ? in.lds_cap : 0);
+  }
+  return p;
 }
 
 }  // namespace pm

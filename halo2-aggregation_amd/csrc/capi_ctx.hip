@@ -175,60 +175,6 @@ int pm_ctx::upload_h2d(void* d, const void* h, size_t bytes, hipStream_t st) {
   return PM_OK;
 }
 
-// ------------------------------------------------------------------- plan
-namespace pm {
-
-static int bit_length(uint32_t v) {
-  int b = 0;
-  while (v) {
-    b++;
-    v >>= 1;
-  }
-  return b;
-}
-
-MsmPlan make_plan(size_t n, int c_override, int min_chunk) {
-  MsmPlan pl;
-  int lg = bit_length((uint32_t)std::max<size_t>(n, 1)) - 1;
-  // auto window: lg - 2 from 2^14 up (capped at 16), lg - 4 below; swept on
-  // MI355X (profiles/r01_s3/c_sweep_*.jsonl): 2^16 c = 14, 2^18 c = 16 (was
-  // lg - 4 everywhere: 2^18 0.85 -> 0.77 ms, 2^16 0.68 -> 0.61 ms)
-  int c = c_override > 0 ? c_override : std::max(4, std::min(kAutoMaxC, lg >= 14 ? lg - 2 : lg - 4));
-  c = std::max(kMinC, std::min(kMaxC, c));
-  pl.c = c;
-  pl.W = (256 + c - 1) / c;
-  pl.base = 256 / pl.W;
-  pl.extra = 256 % pl.W;
-  pl.cmax = pl.base + (pl.extra ? 1 : 0);
-  pl.K = 1 << (pl.cmax - 1);
-  pl.L1 = std::min(kL1, pl.K);
-  pl.log2L1 = bit_length((uint32_t)pl.L1) - 1;
-  pl.NB = ((pl.K + 1 + pl.L1 - 1) / pl.L1) * pl.L1;
-  // segments cover slots [0, K); the top bucket K (the only one past them)
-  // is folded by segment 0's unused slot-0 lane and reaches the host Horner
-  // on its own (weight K): K / L1 is a power of two, so the segment grids
-  // fill whole block rounds (2^20: 2048 blocks of k_bucket_seg_q, not 2049)
-  pl.M1 = pl.K / pl.L1;
-  pl.NB2 = bit_length((uint32_t)(pl.M1 - 1));
-  pl.n = (uint32_t)n;
-  // one window group: round 1 measured pipelined window groups (reduction of
-  // group g beside the accumulation of g-1) slower at every size -- the
-  // reduction kernels compete for the same VALU slots and each smaller
-  // accumulate launch loses occupancy (2^20: G=1 2.29 ms, G=2 2.43, G=4 2.95;
-  // profiles/r01_s2/pipe2) -- and round 3 retired them
-  const size_t work = (size_t)n * pl.W;
-  const size_t target = 256 * 1024;  // lanes in flight: 256 CUs x 16 waves x 64
-  const size_t mc = min_chunk > 0 ? (size_t)min_chunk : 16;
-  pl.chunk = (uint32_t)std::max<size_t>(mc, (work + target - 1) / target);
-  pl.nthreads = (uint32_t)((work + pl.chunk - 1) / pl.chunk);
-  return pl;
-}
-
-// the accumulate work of a table is every window's entries, npad * W: make_plan's over npad points
-MsmPlan make_plan_fixed(size_t npad, int c, int min_chunk) { return make_plan(npad, c, min_chunk); }
-
-}  // namespace pm
-
 // default context per device (lazily created, process lifetime)
 namespace {
 std::mutex g_default_mu;
@@ -281,7 +227,7 @@ int pm_ctx_create(int device, pm_ctx** out) {
     int cus = 0, lds = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     HIP_TRY(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device));
-    if (lds < (int)kLdsPerCu)
+    if (lds < (int)kMaxLds)
       return set_error(PM_ERR_UNSUPPORTED, "device has " + std::to_string(lds) +
                                                " B of LDS per CU; this build needs gfx950's 160 KiB");
     c->num_cus = std::max(1, cus);

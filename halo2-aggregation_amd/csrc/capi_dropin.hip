@@ -31,7 +31,7 @@ constexpr size_t kDigestChunk = size_t(1) << 15;  // points per chunk (2 MiB)
 size_t dropin_bytes(size_t n) {
   const int rows = resident_rows(n);
   if (rows <= 1) return std::max<size_t>(64, n * 64);
-  return (size_t)rows * std::max<size_t>(kFixedPad, (n + kFixedPad - 1) / kFixedPad * kFixedPad) * 64;  // fixed_table's npad
+  return (size_t)rows * std::max<size_t>(kSortB, (n + kSortB - 1) / kSortB * kSortB) * 64;  // fixed_table's npad
 }
 
 bool same_key(const pm::DropinEntry& e, int curve, size_t n, const uint64_t d[4]) {

@@ -87,6 +87,23 @@ int launch_sort(int W, bool d16, const uint32_t* s, uint32_t n, uint32_t canonic
   }
 }
 
+// k_sort_coarse by entry width (then by points per thread, launch_coarse)
+template <bool D16>
+void launch_coarse_w(bool wide, const void* dg, uint32_t ue, const SortGeom& gm, const uint32_t* bofs, void* mid,
+                     dim3 grid, size_t lds, hipStream_t st) {
+  if (!wide) launch_coarse<D16, false>(dg, ue, gm, bofs, mid, grid, lds, st);
+  else launch_coarse<D16, true>(dg, ue, gm, bofs, mid, grid, lds, st);
+}
+
+// k_bucket_seg_q over the nch sorted lists of a call
+template <class F>
+void launch_bucket_seg(int nch, unsigned blocks, hipStream_t st, const SegChunks<F>& co, int Wr, int NB, uint32_t M1,
+                       Xyzz<F>* S, Xyzz<F>* T, Xyzz<F>* Qd, int NQ) {
+  if (nch == 3) k_bucket_seg_q<F, 3><<<blocks, 256, 0, st>>>(co, Wr, NB, M1, S, T, Qd, NQ);
+  else if (nch == 2) k_bucket_seg_q<F, 2><<<blocks, 256, 0, st>>>(co, Wr, NB, M1, S, T, Qd, NQ);
+  else k_bucket_seg_q<F, 1><<<blocks, 256, 0, st>>>(co, Wr, NB, M1, S, T, Qd, NQ);
+}
+
 // Run the device pipeline of one MSM; result = host XYZZ point.
 //
 // Sort once, accumulate every bucket set in one launch, then the bucket
@@ -116,6 +133,150 @@ struct MsmTail {
 template <class F>
 int msm_tail(Ctx* ctx, const MsmTail<F>& t, Xyzz<F>* result);
 
+// each part keeps its sorted list and bucket partials for the reduction
+struct PartBufs {
+  Buf &sorted, &offsets, &buckets, &head;
+};
+inline PartBufs part_bufs(Ctx* ctx, int ch) {
+  if (ch == 0) return PartBufs{ctx->sorted, ctx->offsets, ctx->buckets, ctx->head};
+  return PartBufs{ctx->part_sorted[ch - 1], ctx->part_offsets[ch - 1], ctx->part_buckets[ch - 1],
+                  ctx->part_head[ch - 1]};
+}
+
+// Every device buffer of one MSM call (msm_schedule's sizes), before anything
+// is queued; convert: the call converts its bases into ctx->bases29.
+template <class F>
+int msm_ensure_buffers(Ctx* ctx, const MsmSchedule& sc, size_t n, bool convert) {
+  const MsmPlan& pl = sc.pl;
+  const int Wr = sc.red.Wr;
+  int rc;
+  if ((rc = ctx->segS.ensure((size_t)Wr * pl.M1 * sizeof(Xyzz<F>)))) return rc;
+  if ((rc = ctx->segT.ensure((size_t)Wr * pl.M1 * sizeof(Xyzz<F>)))) return rc;
+  if ((rc = ctx->bitsQ.ensure((size_t)Wr * sc.red.NQ * sizeof(Xyzz<F>)))) return rc;
+  const size_t nQ = (size_t)Wr * sc.red.NQ;
+  if ((rc = ctx->ensure_pinned(2 * nQ * sizeof(Xyzz<F>)))) return rc;  // two slots (batch pipelining)
+  if ((rc = ctx->ensure_group_events(2))) return rc;
+  if (convert && (rc = ctx->bases29.ensure(n * 64))) return rc;
+  // the sort scratch, shared by the parts (their kernels run in stream order),
+  // sized for the largest before anything is queued
+  for (int ch = 0; ch < sc.parts.nch; ch++) {
+    const SortPlan& q = sc.part[ch];
+    if ((rc = ctx->digits.ensure(q.nW * (sc.d16 ? 2 : 4)))) return rc;
+    if ((rc = ctx->mid.ensure(q.nW * (q.wide ? 8 : 4)))) return rc;
+    if ((rc = ctx->counts.ensure(q.TOTB * 4))) return rc;
+    if ((rc = ctx->cursor.ensure(q.TOTB * 4))) return rc;
+    if ((rc = ctx->bsum.ensure((size_t)q.nb * 4))) return rc;
+    const PartBufs b = part_bufs(ctx, ch);
+    if ((rc = b.sorted.ensure(q.nW * 4))) return rc;
+    if ((rc = b.offsets.ensure(sc.red.TOT * 4))) return rc;
+    if ((rc = b.buckets.ensure((size_t)Wr * pl.NB * sizeof(Xyzz<F>)))) return rc;
+    if ((rc = b.head.ensure((size_t)q.nthreads * sizeof(Xyzz<F>)))) return rc;
+  }
+  return PM_OK;
+}
+
+// Sort and accumulate part ch of an MSM on the context stream (its scalars
+// first, when they are still in host memory); *out describes its bucket
+// partials to the reduction.
+template <class Cv>
+int msm_enqueue_part(Ctx* ctx, const MsmSchedule& sc, int ch, const uint32_t* d_scalars, const void* h_scalars,
+                     const uint32_t* bases29, uint32_t canon, SegChunk<typename Cv::Base>* out) {
+  using F = typename Cv::Base;
+  using Fs = typename Cv::Scalar;
+  const MsmPlan& pl = sc.pl;
+  const SortPlan& q = sc.part[ch];
+  const hipStream_t st = ctx->stream, cs = st;
+  const int Wr = sc.red.Wr;
+  int rc;
+  SortGeom g = q.g;
+  const SortGeom& gm = q.gm;
+  const PartBufs b = part_bufs(ctx, ch);
+  uint32_t* sorted = (uint32_t*)b.sorted.p;
+  void* mid = ctx->mid.p;
+  uint32_t* bh = (uint32_t*)ctx->counts.p;
+  uint32_t* bofs = (uint32_t*)ctx->cursor.p;
+  uint32_t* offsets = (uint32_t*)b.offsets.p;
+  uint32_t* bsum = (uint32_t*)ctx->bsum.p;
+  Xyzz<F>* buckets = (Xyzz<F>*)b.buckets.p;
+  Xyzz<F>* head = (Xyzz<F>*)b.head.p;
+  g.clr_bh = bh + (q.TOTB - 1);  // zeroed by the histogram kernel's block 0
+  const uint32_t* sc0 = d_scalars + 8 * q.c0;
+  if (h_scalars) {
+    // one pageable copy ahead of this part's histogram pass (without the
+    // split: a copy in 4 chunks, each chunk's histogram blocks launched
+    // behind it, measured ~0.1 ms slower per 2^20 MSM: round 3,
+    // profiles/r03/h2d/)
+    const hipStream_t xs = ch == 0 ? st : ctx->copy_stream;
+    if ((rc = ctx->upload_h2d((void*)sc0, (const uint8_t*)h_scalars + 32 * q.c0, q.nc * 32, xs))) return rc;
+    if (ch > 0) {
+      hipEvent_t evc = ctx->next_event();
+      if (!evc) return set_error(PM_ERR_HIP, "hipEventCreate failed");
+      HIP_TRY(hipEventRecord(evc, xs));
+      HIP_TRY(hipStreamWaitEvent(st, evc, 0));
+    }
+  }
+  PM_LAUNCH_ST(ctx, cs, "sort_hist", rc = launch_sort<Fs>(pl.W, sc.d16, sc0, (uint32_t)q.nc, canon, g, g.nblk, bh,
+                                                          ctx->digits.p, (uint32_t)q.stride, (uint32_t)sc.kmerge, cs));
+  if (rc) return rc;
+  PM_LAUNCH_ST(ctx, cs, "scan", {
+    k_scan_reduce<<<q.nb, kScanThreads, 0, cs>>>(bh, (uint32_t)q.TOTB, q.tiles, bsum);
+    k_scan_down<<<q.nb, kScanThreads, 0, cs>>>(bh, (uint32_t)q.TOTB, q.tiles, bsum, bofs, nullptr);
+  });
+  {
+    const dim3 grid(gm.nblk / gm.hsub, Wr);
+    const uint32_t ue = (uint32_t)q.E;
+    if (sc.d16)
+      PM_LAUNCH_ST(ctx, cs, "sort_coarse",
+                   launch_coarse_w<true>(q.wide, ctx->digits.p, ue, gm, bofs, mid, grid, q.lds_coarse, cs));
+    else
+      PM_LAUNCH_ST(ctx, cs, "sort_coarse",
+                   launch_coarse_w<false>(q.wide, ctx->digits.p, ue, gm, bofs, mid, grid, q.lds_coarse, cs));
+  }
+  if (q.wide)
+    PM_LAUNCH_ST(ctx, cs, "sort_fine", (k_sort_fine<true><<<Wr * g.NCB, kFineThreads, q.lds_fine, cs>>>(
+                                          (const uint64_t*)mid, bofs, gm, Wr, pl.NB, (uint32_t)q.cache_n,
+                                          (uint32_t)q.chn, offsets, sorted)));
+  else
+    PM_LAUNCH_ST(ctx, cs, "sort_fine", (k_sort_fine<false><<<Wr * g.NCB, kFineThreads, q.lds_fine, cs>>>(
+                                          (const uint32_t*)mid, bofs, gm, Wr, pl.NB, (uint32_t)q.cache_n,
+                                          (uint32_t)q.chn, offsets, sorted)));
+  const uint32_t s1 = (uint32_t)((size_t)Wr * pl.NB);
+  PM_LAUNCH_ST(ctx, cs, "accumulate",
+               (k_accumulate<F><<<(q.nthreads + 255) / 256, 256, 0, cs>>>(sorted, offsets, s1, bases29, q.chunk,
+                                                                          buckets, head)));
+  *out = SegChunk<F>{offsets, q.chunk, q.nthreads, buckets, head};
+  return PM_OK;
+}
+
+// The bucket reduction over the parts' partials: the host terms land in the
+// pinned slot's device alias Qd.
+template <class F>
+int msm_enqueue_reduce(Ctx* ctx, const MsmSchedule& sc, const SegChunks<F>& co, Xyzz<F>* Qd) {
+  const MsmPlan& pl = sc.pl;
+  const ReducePlan& rd = sc.red;
+  const hipStream_t st = ctx->stream;
+  const int Wr = rd.Wr, NJ = rd.NJ, NQ = rd.NQ, nsplit = rd.nsplit;
+  Xyzz<F>* S = (Xyzz<F>*)ctx->segS.p;
+  Xyzz<F>* T = (Xyzz<F>*)ctx->segT.p;
+  int rc;
+  PM_LAUNCH(ctx, "bucket_seg",
+            launch_bucket_seg<F>(sc.parts.nch, rd.seg_blocks, st, co, Wr, pl.NB, (uint32_t)pl.M1, S, T, Qd, NQ));
+  Xyzz<F>* bitsP = nullptr;
+  uint32_t* tickets = nullptr;
+  if (nsplit > 1) {
+    if ((rc = ctx->bitsP.ensure((size_t)Wr * NJ * nsplit * sizeof(Xyzz<F>)))) return rc;
+    const size_t old_cap = ctx->tickets.cap;  // tickets are self-resetting; zero fresh allocations
+    if ((rc = ctx->tickets.ensure((size_t)Wr * NJ * 4))) return rc;
+    if (ctx->tickets.cap != old_cap) HIP_TRY(hipMemsetAsync(ctx->tickets.p, 0, ctx->tickets.cap, st));
+    bitsP = (Xyzz<F>*)ctx->bitsP.p;
+    tickets = (uint32_t*)ctx->tickets.p;
+  }
+  PM_LAUNCH(ctx, "bucket_bits",
+            (k_bucket_bits<F><<<dim3(NJ, Wr, nsplit), kRedThreads, 0, st>>>(S, T, pl.M1, pl.NB2, Qd, NQ, nsplit,
+                                                                             bitsP, tickets)));
+  return PM_OK;
+}
+
 // Enqueue the device pipeline of one MSM (everything up to the D2H copy of
 // its host terms into pinned slot `slot`) and describe its host tail in
 // *tail; msm_tail then waits for it and runs the Horner.  Two MSMs can be in
@@ -124,12 +285,15 @@ int msm_tail(Ctx* ctx, const MsmTail<F>& t, Xyzz<F>* result);
 //
 // h_scalars != nullptr: the scalars are still in (pageable) host memory and
 // d_scalars is their device buffer; they are copied ahead of the sort.
+//
+// Four steps: the plan (msm_plan.hpp msm_schedule: window plan, the split
+// scalar copy's parts, each part's sort geometry, the reduction's grids),
+// the buffers, each part's sort and accumulation, the reduction.
 template <class Cv>
 int msm_device_impl(Ctx* ctx, const uint32_t* d_scalars, const uint32_t* d_bases, size_t n, uint32_t flags,
                     Xyzz<typename Cv::Base>* result, const pm_fixed_bases* ft = nullptr,
                     MsmTail<typename Cv::Base>* tail = nullptr, int slot = 0, const void* h_scalars = nullptr) {
   using F = typename Cv::Base;
-  using Fs = typename Cv::Scalar;
   if (n == 0) {
     if (tail) *tail = MsmTail<F>{};
     else *result = xyzz_inf<F>();
@@ -139,59 +303,27 @@ int msm_device_impl(Ctx* ctx, const uint32_t* d_scalars, const uint32_t* d_bases
   const bool fixed = ft != nullptr;
   // pre29: resident bases already in the pipeline's R = 2^261 form (pm_bases)
   const bool pre29 = !fixed && (flags & kBasesR261) != 0;
-  const MsmPlan pl = fixed ? make_plan_fixed(ft->npad, ft->c, ctx->min_chunk)
-                           : make_plan(n, ctx->window_c, ctx->min_chunk);
+  MsmShape shape{};
+  shape.n = n;
+  shape.fixed = fixed;
+  shape.npad = fixed ? ft->npad : 0;
+  shape.fixed_c = fixed ? ft->c : 0;
+  shape.rows = fixed ? ft->rows : 1;
+  shape.host_scalars = h_scalars != nullptr;
+  shape.window_c = ctx->window_c;
+  shape.min_chunk = ctx->min_chunk;
+  shape.split_copy = ctx->msm_split_copy;
+  shape.fine_cache_kb = ctx->fine_cache_kb;
+  shape.fine_chunk_kb = ctx->fine_chunk_kb;
+  const MsmSchedule sc = msm_schedule(shape);
+  if (sc.err == kPlanFineTooWide) return set_error(PM_ERR_UNSUPPORTED, "sort: fine bits too wide");
+  const MsmPlan& pl = sc.pl;
   const hipStream_t st = ctx->stream;
-  const int kmerge = fixed ? ft->rows : 1;
-  const int Wr = pl.W / kmerge;                     // bucket sets (reduced windows)
-  const size_t TOT = (size_t)Wr * pl.NB + 1;
-  const int NJ = pl.NB2 + kTJobs;                   // bit-sum jobs per set
-  const int NQ = NJ + 1;                            // host terms per set
-  const bool d16 = pl.cmax <= 16;
-  // Split scalar copy (round 6): a row-table MSM with scalars in host memory
-  // sorts and accumulates a first part of its points while the rest of the
-  // scalars cross PCIe.  A pageable hipMemcpyAsync blocks the calling thread
-  // for the whole copy but overlaps kernels on other streams
-  // (tools/h2d_overlap.hip: 32 MB in 0.60 ms, 2 x 16 MB 0.62, a 0.45 ms kernel
-  // meanwhile hidden), so: copy part 0 on the context stream (blocks), queue
-  // its sort and accumulation there, copy part 1 on the copy stream (blocks
-  // while part 0 runs), then queue part 1's sort and accumulation on the
-  // context stream behind an event of that copy, and one bucket reduction
-  // over both sorted lists (k_bucket_seg_q<F, 2>).  Part 1's kernels stay on
-  // the context stream: beside part 0's accumulation on a queue of their own
-  // they only slowed it (sort 0.10 -> 0.27 ms, accumulation 0.49 -> 0.52,
-  // same end; rocprofv3 trace, round 6).  Each part is sorted as a table of
-  // its own points (digit rows of its padded length) and k_sort_coarse
-  // writes the full table's indices.
-  const int nch = fixed && h_scalars && ctx->msm_split_copy != 0 && n >= kSplitCopyMinN
-                      ? (n >= kSplitCopy3MinN ? 3 : 2) : 1;
-  // Two parts: the first is 3/8 of the points -- its copy is the exposed one,
-  // and the second part's copy (5/8) still ends before the first part's sort
-  // and accumulation do (2^20 with host scalars: 1/2 1.61 ms, 5/16
-  // 1.57-1.58, 3/8 1.57, 7/16 1.64; 2^22: 3/8 5.68 ms, 1/2 6.00 ms, one copy
-  // 7.3-7.4).  Three parts (1/4, 3/8, 3/8) from kSplitCopy3MinN points: the
-  // exposed copy shrinks with n while each extra part costs a fixed sort
-  // (~0.04 ms) and chain fold (2^20: 1.64-1.68 ms against 1.59-1.62 with two;
-  // 2^22: 5.25-5.32 against 5.63-5.66; profiles/r06/split_copy_ab.jsonl)
-  // part starts (multiples of kSortB): two parts 3/8 + 5/8, three 1/4 + 3/8 + 3/8
-  size_t pstart[kMaxParts + 1] = {0, n, n, n};
-  auto rnd = [](size_t v) { return (v + kSortB - 1) / kSortB * kSortB; };
-  if (nch == 2) pstart[1] = rnd(n * 3 / 8);
-  if (nch == 3) {
-    pstart[1] = rnd(n / 4);
-    pstart[2] = rnd(n * 5 / 8);
-  }
-  pstart[nch] = n;
+  const int nch = sc.parts.nch;
   int rc;
-  if ((rc = ctx->segS.ensure((size_t)Wr * pl.M1 * sizeof(Xyzz<F>)))) return rc;
-  if ((rc = ctx->segT.ensure((size_t)Wr * pl.M1 * sizeof(Xyzz<F>)))) return rc;
-  if ((rc = ctx->bitsQ.ensure((size_t)Wr * NQ * sizeof(Xyzz<F>)))) return rc;
-  const size_t nQ = (size_t)Wr * NQ;
-  if ((rc = ctx->ensure_pinned(2 * nQ * sizeof(Xyzz<F>)))) return rc;  // two slots (batch pipelining)
-  if ((rc = ctx->ensure_group_events(2))) return rc;
+  if ((rc = msm_ensure_buffers<F>(ctx, sc, n, !fixed && !pre29))) return rc;
+  const size_t nQ = (size_t)sc.red.Wr * sc.red.NQ;
   Xyzz<F>* hslot = (Xyzz<F>*)ctx->h_pinned + (size_t)slot * nQ;
-  Xyzz<F>* S = (Xyzz<F>*)ctx->segS.p;
-  Xyzz<F>* T = (Xyzz<F>*)ctx->segT.p;
   // host terms: the reduction kernels store them straight into the pinned
   // slot (mapped; visible to the host once the event below completes), which
   // saves the blit of a D2H copy (~11 us per MSM, profiles/r03/kernel_stats.csv
@@ -209,7 +341,6 @@ int msm_device_impl(Ctx* ctx, const uint32_t* d_scalars, const uint32_t* d_bases
   } else if (pre29) {
     bases29 = d_bases;
   } else {
-    if ((rc = ctx->bases29.ensure(n * 64))) return rc;
     bases29 = (const uint32_t*)ctx->bases29.p;
     PM_LAUNCH(ctx, "bases_r261",
               (k_bases_to_r261<F><<<(un + 255) / 256, 256, 0, st>>>(d_bases, un, (uint32_t*)ctx->bases29.p)));
@@ -223,228 +354,14 @@ int msm_device_impl(Ctx* ctx, const uint32_t* d_scalars, const uint32_t* d_bases
     HIP_TRY(hipEventRecord(ev0, st));
     HIP_TRY(hipStreamWaitEvent(ctx->copy_stream, ev0, 0));
   }
-  // sort geometry of a digit row length (the whole MSM's, or a part's)
-  struct PartGeom {
-    size_t E, nW, TOTB;
-    SortGeom g, gm;
-    ScanTiles tiles;
-    uint32_t nb;
-    bool wide;
-  };
-  auto geom = [&](size_t stride) {
-    PartGeom r{};
-    r.E = (size_t)kmerge * stride;  // entries of one sort row
-    r.nW = (size_t)stride * pl.W;
-    SortGeom& g = r.g;  // histogram geometry (blocks of scalars)
-    g.FB = std::max(0, pl.cmax - 1 - 8);
-    // the fixed-base MSM's merged sort rows are W x longer: 4x more coarse bins
-    // once they exceed 2^24 entries (2^23, c = 20: FB 11 -> 9, sort 3.4 -> 2.3 ms)
-    if (fixed && r.E > (size_t(1) << 24)) g.FB = std::max(0, pl.cmax - 1 - 10);
-    g.NCB = (pl.K >> g.FB) + 1;
-    // points per thread: blocks of 1024 threads x ppt points, ppt the largest
-    // power of two <= 8 that still gives >= 128 blocks (2^20: 8192 points per
-    // block; larger blocks give longer contiguous runs per coarse bin in
-    // k_sort_coarse and a 4x smaller block histogram to scan: sort 0.19 ->
-    // 0.16 ms at 2^20; small n keeps enough blocks)
-    g.ppt = 1;
-    while (g.ppt < kSortPerThread && stride >= (size_t)256 * g.ppt * kSortThreads) g.ppt *= 2;
-    g.nblk = (int)((stride + (size_t)g.ppt * kSortThreads - 1) / ((size_t)g.ppt * kSortThreads));
-    // The histogram pass is compute-bound per block (Montgomery -> canonical,
-    // W signed digits and LDS atomics per scalar); with 8192-point blocks 2^20
-    // gives 128 blocks for 256 CUs.  Split each coarse block's points over 2
-    // histogram blocks when the grid is short of the CUs: the coarse pass keeps
-    // its long runs and reads its start offsets at every hsub-th histogram
-    // block.  The scan doubles with it, so one split only (same box, 2^20:
-    // histogram 0.049-0.050 -> 0.035-0.041 ms, scan 0.014 -> 0.019 ms; below
-    // 128 blocks the scan's growth cancels the gain: 2^19 +-0, 2^18 +3-5 us,
-    // profiles/r02/hs/ab.txt and profiles/r02/p/ab.txt).
-    int hsub = 1;
-    if (g.ppt >= 2 && g.nblk >= 128 && g.nblk < 256) hsub = 2;
-    g.hsub = 1;
-    r.gm = g;         // coarse / fine geometry (blocks of sort-row entries)
-    g.ppt /= hsub;    // histogram geometry
-    g.nblk *= hsub;
-    r.gm.nblk = g.nblk * kmerge;
-    r.gm.hsub = hsub;
-    r.TOTB = (size_t)pl.W * g.NCB * g.nblk + 1;
-    r.tiles = scan_tiles((uint32_t)(pl.W * g.NCB), (uint32_t)g.nblk);  // k_sort_hist's layout
-    r.nb = (uint32_t)((r.TOTB + r.tiles.chunk - 1) / r.tiles.chunk);
-    // 4-B coarse entries when the entry index fits beside the fine bits and
-    // the sign (a part's entries carry the full table's indices)
-    const size_t imax = nch > 1 ? (size_t)kmerge * ft->npad : r.E;
-    r.wide = imax > (size_t(1) << (31 - g.FB));
-    return r;
-  };
-  // digit row length: n, the table's padded rows, or a part's own padded length
-  auto part_stride = [&](int ch) -> size_t {
-    return !fixed ? n : nch > 1 ? std::max<size_t>(kSortB, rnd(pstart[ch + 1] - pstart[ch])) : ft->npad;
-  };
-  // the sort scratch, shared by the parts (their kernels run in stream order),
-  // sized for the largest before anything is queued
-  for (int ch = 0; ch < nch; ch++) {
-    const PartGeom q = geom(part_stride(ch));
-    if ((rc = ctx->digits.ensure(q.nW * (d16 ? 2 : 4)))) return rc;
-    if ((rc = ctx->mid.ensure(q.nW * (q.wide ? 8 : 4)))) return rc;
-    if ((rc = ctx->counts.ensure(q.TOTB * 4))) return rc;
-    if ((rc = ctx->cursor.ensure(q.TOTB * 4))) return rc;
-    if ((rc = ctx->bsum.ensure((size_t)q.nb * 4))) return rc;
-  }
-  for (int ch = 0; ch < nch; ch++) {
-    const hipStream_t cs = st;
-    const size_t c0 = pstart[ch], nc = pstart[ch + 1] - c0;
-    const size_t stride = part_stride(ch);
-    const PartGeom q = geom(stride);
-    const size_t E = q.E, nW = q.nW, TOTB = q.TOTB;
-    SortGeom g = q.g;
-    SortGeom gm = q.gm;
-    const ScanTiles tiles = q.tiles;
-    const uint32_t nb = q.nb;
-    const bool wide = q.wide;
-    // a part's entries carry table indices j npad + c0 + i (k_sort_coarse)
-    gm.rstride = (uint32_t)stride;
-    gm.rdelta = nch > 1 ? (uint32_t)(ft->npad - stride) : 0u;
-    gm.roff = nch > 1 ? (uint32_t)c0 : 0u;
-    // each part keeps its sorted list and bucket partials for the reduction
-    Buf& b_digits = ctx->digits;
-    Buf& b_mid = ctx->mid;
-    Buf& b_counts = ctx->counts;
-    Buf& b_cursor = ctx->cursor;
-    Buf& b_bsum = ctx->bsum;
-    Buf& b_sorted = ch ? ctx->part_sorted[ch - 1] : ctx->sorted;
-    Buf& b_offsets = ch ? ctx->part_offsets[ch - 1] : ctx->offsets;
-    Buf& b_buckets = ch ? ctx->part_buckets[ch - 1] : ctx->buckets;
-    Buf& b_head = ch ? ctx->part_head[ch - 1] : ctx->head;
-    // accumulation lanes: each part's own plan (~4 waves per SIMD; a part's
-    // buckets reach as many slices as a full sort's).  The whole MSM's slice
-    // length instead (fewer lanes, shorter chains) measured the same with
-    // equal halves and 0.17 ms slower with a 3/8 first part (1.5 waves per
-    // SIMD in its accumulation)
-    const uint32_t chunk = nch > 1 ? make_plan_fixed(stride, ft->c, ctx->min_chunk).chunk : pl.chunk;
-    const uint32_t nthreads = nch > 1 ? (uint32_t)((nW + chunk - 1) / chunk) : pl.nthreads;
-    if ((rc = b_sorted.ensure(nW * 4))) return rc;
-    if ((rc = b_offsets.ensure(TOT * 4))) return rc;
-    if ((rc = b_buckets.ensure((size_t)Wr * pl.NB * sizeof(Xyzz<F>)))) return rc;
-    if ((rc = b_head.ensure((size_t)nthreads * sizeof(Xyzz<F>)))) return rc;
-
-    uint32_t* sorted = (uint32_t*)b_sorted.p;
-    void* mid = b_mid.p;
-    uint32_t* bh = (uint32_t*)b_counts.p;
-    uint32_t* bofs = (uint32_t*)b_cursor.p;
-    uint32_t* offsets = (uint32_t*)b_offsets.p;
-    uint32_t* bsum = (uint32_t*)b_bsum.p;
-    Xyzz<F>* buckets = (Xyzz<F>*)b_buckets.p;
-    Xyzz<F>* head = (Xyzz<F>*)b_head.p;
-    g.clr_bh = bh + (TOTB - 1);  // zeroed by the histogram kernel's block 0
-    const uint32_t* sc = d_scalars + 8 * c0;
-    const uint32_t unc = (uint32_t)nc;
-    if (h_scalars) {
-      // one pageable copy ahead of this part's histogram pass (without the
-      // split: a copy in 4 chunks, each chunk's histogram blocks launched
-      // behind it, measured ~0.1 ms slower per 2^20 MSM: round 3,
-      // profiles/r03/h2d/)
-      const hipStream_t xs = ch == 0 ? st : ctx->copy_stream;
-      if ((rc = ctx->upload_h2d((void*)sc, (const uint8_t*)h_scalars + 32 * c0, nc * 32, xs))) return rc;
-      if (ch > 0) {
-        hipEvent_t evc = ctx->next_event();
-        if (!evc) return set_error(PM_ERR_HIP, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(evc, xs));
-        HIP_TRY(hipStreamWaitEvent(st, evc, 0));
-      }
-    }
-    PM_LAUNCH_ST(ctx, cs, "sort_hist", rc = launch_sort<Fs>(pl.W, d16, sc, unc, canon, g, g.nblk, bh, b_digits.p,
-                                                            (uint32_t)stride, (uint32_t)kmerge, cs));
-    if (rc) return rc;
-    PM_LAUNCH_ST(ctx, cs, "scan", {
-      k_scan_reduce<<<nb, kScanThreads, 0, cs>>>(bh, (uint32_t)TOTB, tiles, bsum);
-      k_scan_down<<<nb, kScanThreads, 0, cs>>>(bh, (uint32_t)TOTB, tiles, bsum, bofs, nullptr);
-    });
-    {
-      const size_t lds = (size_t)gm.ppt * kSortThreads * ((wide ? 8 : 4) + 2) + (size_t)(2 * g.NCB + 1) * 4 + (kSortThreads / 64 + 1) * 4;
-      const dim3 grid(gm.nblk / gm.hsub, Wr);
-      void* dg = b_digits.p;
-      const uint32_t ue = (uint32_t)E;
-      if (d16 && !wide)
-        PM_LAUNCH_ST(ctx, cs, "sort_coarse", launch_coarse<true, false>(dg, ue, gm, bofs, mid, grid, lds, cs));
-      else if (d16)
-        PM_LAUNCH_ST(ctx, cs, "sort_coarse", launch_coarse<true, true>(dg, ue, gm, bofs, mid, grid, lds, cs));
-      else if (!wide)
-        PM_LAUNCH_ST(ctx, cs, "sort_coarse", launch_coarse<false, false>(dg, ue, gm, bofs, mid, grid, lds, cs));
-      else
-        PM_LAUNCH_ST(ctx, cs, "sort_coarse", launch_coarse<false, true>(dg, ue, gm, bofs, mid, grid, lds, cs));
-    }
-    // fine sort LDS: segment cache + chunk buffer (k_sort_fine).  A mean
-    // segment that fits 24 KiB is cached whole with room for 1.5x its size and
-    // sorted as one chunk; larger ones are re-read from mid in 32 KiB chunks
-    // (2 blocks per CU).  Sweep with 16-B loads (profiles/r03/sort_fine/): 16
-    // KiB chunks 2^20 0.065 / 2^22 0.233 ms, 24-32 KiB 0.056 / 0.210, 40-64 KiB
-    // (one block per CU) 0.064-0.074 / 0.256-0.288; the whole segment cached in
-    // LDS (64-136 KiB) 0.069-0.107 / 0.34-0.44.  PM_FINE_CACHE_KB /
-    // PM_FINE_CHUNK_KB override both (A/B).
-    const size_t esz = wide ? 8 : 4;
-    const size_t mean_seg = E / std::max(1, g.NCB - 1) + 1;
-    const size_t fine_fixed = ((size_t)3 * (1 << g.FB) + kFineThreads / 64 + 1) * 4;  // hist, lcur, lst, scan
-    size_t cache_n = (mean_seg * 3 / 2 + 63) & ~size_t(63), chn;
-    if (cache_n * esz > 24576) cache_n = kFineChunkBytes / esz;
-    chn = cache_n;
-    if (ctx->fine_cache_kb > 0) cache_n = ((size_t)ctx->fine_cache_kb * 1024 / esz) & ~size_t(63);
-    if (ctx->fine_chunk_kb > 0) chn = ((size_t)ctx->fine_chunk_kb * 1024 / esz) & ~size_t(63);
-    chn = std::max<size_t>(64, std::min(chn, cache_n));
-    cache_n = std::max(cache_n, chn);
-    if (fine_fixed + 128 * esz > kMaxLds) return set_error(PM_ERR_UNSUPPORTED, "sort: fine bits too wide");
-    while (cache_n > 64 && (cache_n + chn) * esz + fine_fixed > kMaxLds) {
-      cache_n /= 2;
-      chn = std::min(chn, cache_n);
-    }
-    const size_t lds_fine = (cache_n + chn) * esz + fine_fixed;
-    if (wide)
-      PM_LAUNCH_ST(ctx, cs, "sort_fine", (k_sort_fine<true><<<Wr * g.NCB, kFineThreads, lds_fine, cs>>>(
-                                            (const uint64_t*)mid, bofs, gm, Wr, pl.NB, (uint32_t)cache_n, (uint32_t)chn,
-                                            offsets, sorted)));
-    else
-      PM_LAUNCH_ST(ctx, cs, "sort_fine", (k_sort_fine<false><<<Wr * g.NCB, kFineThreads, lds_fine, cs>>>(
-                                            (const uint32_t*)mid, bofs, gm, Wr, pl.NB, (uint32_t)cache_n, (uint32_t)chn,
-                                            offsets, sorted)));
-    const uint32_t s1 = (uint32_t)((size_t)Wr * pl.NB);
-    PM_LAUNCH_ST(ctx, cs, "accumulate",
-                 (k_accumulate<F><<<(nthreads + 255) / 256, 256, 0, cs>>>(sorted, offsets, s1, bases29, chunk,
-                                                                          buckets, head)));
-    co.c[ch] = SegChunk<F>{offsets, chunk, nthreads, buckets, head};
-  }
-  // chains (long ones wave-cooperatively) + segment sums + the top bucket
-  const unsigned seg_blocks = (unsigned)((4ull * Wr * pl.M1 + 255) / 256);
-  if (nch == 3)
-    PM_LAUNCH(ctx, "bucket_seg", (k_bucket_seg_q<F, 3><<<seg_blocks, 256, 0, st>>>(co, Wr, pl.NB, (uint32_t)pl.M1, S, T,
-                                                                                   Qd, NQ)));
-  else if (nch == 2)
-    PM_LAUNCH(ctx, "bucket_seg", (k_bucket_seg_q<F, 2><<<seg_blocks, 256, 0, st>>>(co, Wr, pl.NB, (uint32_t)pl.M1, S, T,
-                                                                                   Qd, NQ)));
-  else
-    PM_LAUNCH(ctx, "bucket_seg", (k_bucket_seg_q<F, 1><<<seg_blocks, 256, 0, st>>>(co, Wr, pl.NB, (uint32_t)pl.M1, S, T,
-                                                                                   Qd, NQ)));
-  // bit sums of few sets (the row tables, the fixed-base MSM's one set) are
-  // split over more blocks.  Every extra lane also adds one tree addition, so
-  // the split stops at ~16 blocks per job (c = 20, 2^19 buckets: 16 -> 0.33
-  // ms, 64 -> 0.47 ms; round 3, 16 / Wr against 4, 8, 32, 64 / Wr at 2^19 -
-  // 2^22, resident and raw: profiles/r03/ab/bits_split_sweep.jsonl).
-  const int nsplit = std::max(1, std::min(kMaxSplit, kBitsSplitK / Wr));
-  Xyzz<F>* bitsP = nullptr;
-  uint32_t* tickets = nullptr;
-  if (nsplit > 1) {
-    if ((rc = ctx->bitsP.ensure((size_t)Wr * NJ * nsplit * sizeof(Xyzz<F>)))) return rc;
-    const size_t old_cap = ctx->tickets.cap;  // tickets are self-resetting; zero fresh allocations
-    if ((rc = ctx->tickets.ensure((size_t)Wr * NJ * 4))) return rc;
-    if (ctx->tickets.cap != old_cap) HIP_TRY(hipMemsetAsync(ctx->tickets.p, 0, ctx->tickets.cap, st));
-    bitsP = (Xyzz<F>*)ctx->bitsP.p;
-    tickets = (uint32_t*)ctx->tickets.p;
-  }
-  PM_LAUNCH(ctx, "bucket_bits",
-            (k_bucket_bits<F><<<dim3(NJ, Wr, nsplit), kRedThreads, 0, st>>>(S, T, pl.M1, pl.NB2, Qd, NQ, nsplit,
-                                                                             bitsP, tickets)));
+  for (int ch = 0; ch < nch; ch++)
+    if ((rc = msm_enqueue_part<Cv>(ctx, sc, ch, d_scalars, h_scalars, bases29, canon, &co.c[ch]))) return rc;
+  if ((rc = msm_enqueue_reduce<F>(ctx, sc, co, Qd))) return rc;
   hipEvent_t ev = ctx->grp_ev[slot];
   HIP_TRY(hipEventRecord(ev, st));
   MsmTail<F> t;
-  t.Wr = Wr;
-  t.NQ = NQ;
+  t.Wr = sc.red.Wr;
+  t.NQ = sc.red.NQ;
   t.NB2 = pl.NB2;
   t.base = pl.base;
   t.extra = pl.extra;
@@ -731,25 +648,15 @@ int msm_small_impl(Ctx* ctx, const void* scalars, bool s_host, const void* bases
   if (n > kSmallLimit) return set_error(PM_ERR_UNSUPPORTED, "small-MSM path: n above its limit");
   const hipStream_t st = ctx->stream;
   const uint32_t un = (uint32_t)n, T = 2u * un;
-  const bool fused = un <= kSmallFusedN;
-  // slices per window: up to kSmallSlices blocks of 64 quads (or, from 4096
-  // terms, 256 lanes with one-lane additions), each adding kq terms serially.
-  // Measured (profiles/r04/small/ab.jsonl, n = 256 .. 8192, quads / lanes x
-  // 4 .. 32 slices): 8 slices best at every size, lanes ahead from n = 2048
-  // (121 vs 132 us; 4096: 138 vs 167 us), even at 1024.
-  constexpr uint32_t kSmallSlices = 8;
-  const bool lanes = T >= 4096u;
-  const uint32_t per = lanes ? 256u : (uint32_t)kSmallQuads;  // terms per block and round
+  // fused / quads / lanes and the slices per window: msm_plan.hpp small_plan
+  const SmallPlan sp = small_plan(n);
+  const bool fused = sp.fused, lanes = sp.lanes;
   SmallGeom g{};
   g.n = un;
   g.canonical = (flags & PM_SCALARS_CANONICAL) ? 1u : 0u;
   g.r261 = b_r261 ? 1u : 0u;
-  g.kq = std::max<uint32_t>(1u, (T + per * kSmallSlices - 1) / (per * kSmallSlices));
-  g.ns = (T + per * g.kq - 1) / (per * g.kq);
-  if (fused) {  // one term per quad: 64 per slice
-    g.kq = 1;
-    g.ns = (T + kSmallQuads - 1) / kSmallQuads;
-  }
+  g.kq = sp.kq;
+  g.ns = sp.ns;
   int rc;
   const uint32_t* ds = (const uint32_t*)scalars;
   const uint32_t* db = (const uint32_t*)bases;
@@ -918,7 +825,6 @@ int msm_resident_batch_impl(Ctx* ctx, const void* d_bases29, const pm_fixed_base
 
 // Build a fixed-base table (pm_fixed_bases_create): ft->n, ft->c set by the
 // caller; fills W, npad and the device table.
-static_assert(kFixedPad == kSortB && kLdsPerCu == kMaxLds, "runtime.hpp's copies of the kernels' geometry");
 template <class Cv>
 int fixed_table_impl(Ctx* ctx, const void* d_bases, pm_fixed_bases* ft) {
   using F = typename Cv::Base;

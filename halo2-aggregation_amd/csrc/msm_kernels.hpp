@@ -28,6 +28,7 @@
 #pragma once
 #include "coop29.hpp"
 #include "curve29.hpp"
+#include "msm_plan.hpp"
 
 namespace pm {
 
@@ -93,9 +94,7 @@ struct WinGeom {
 };
 
 // ----------------------------------------------------------------- 2. scan
-constexpr int kScanThreads = 256;
-constexpr int kScanPerThread = 16;
-constexpr int kScanChunk = kScanThreads * kScanPerThread;
+// kScanThreads, kScanPerThread, kScanChunk: msm_plan.hpp
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
   const int lane = threadIdx.x & 63;
@@ -129,24 +128,7 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* lds, u
   return r;
 }
 
-// The block histograms are stored in tiles (k_sort_hist): rows of `nblk`
-// block counters, R = kScanChunk / nblk rows per tile, and inside a tile
-// block-major (counter (row, blk) at blk * Rt + row % R, Rt = the tile's
-// rows), so each histogram block writes runs of Rt counters instead of one
-// 4-B store per row (2^20: 8 us, 2^22: 24 us of strided stores before).  A
-// scan block covers one tile (chunk = R nblk) and reads it in logical
-// (row, blk) order; R = 1 (nblk > kScanChunk / 2) is the plain row-major
-// layout with chunk = kScanChunk.
-struct ScanTiles {
-  uint32_t chunk;  // counters per scan block (one tile)
-  uint32_t R;      // rows per tile (1: row-major)
-  uint32_t nblk;   // counters per row
-  uint32_t rows;   // histogram rows (the sentinel follows them)
-};
-__host__ __device__ inline ScanTiles scan_tiles(uint32_t rows, uint32_t nblk) {
-  const uint32_t R = nblk <= (uint32_t)kScanChunk / 2 ? (uint32_t)kScanChunk / nblk : 1u;
-  return ScanTiles{R > 1 ? R * nblk : (uint32_t)kScanChunk, R, nblk, rows};
-}
+// ScanTiles / scan_tiles (the tiled layout of the block histograms): msm_plan.hpp
 // physical index of histogram counter (row, blk)
 __device__ __forceinline__ size_t tile_index(const ScanTiles& t, uint32_t row, uint32_t blk) {
   if (t.R == 1) return (size_t)row * t.nblk + blk;
@@ -232,35 +214,7 @@ static __global__ void __launch_bounds__(kScanThreads) k_scan_down(const uint32_
 // Traffic per scalar at c = 16 (W = 16): 32 B read, 32 B digits written and
 // read, 64 B entries written and read once, 64 B sorted written (~290 B; was
 // ~600 B with 4-B digits, 8-B entries and two global passes in k_sort_fine).
-constexpr int kSortThreads = 1024;
-constexpr int kSortPerThread = 8;                      // max points per thread (SortGeom::ppt)
-constexpr int kSortB = kSortThreads * kSortPerThread;  // max points per block (fixed-base padding)
-constexpr uint32_t kFineChunkBytes = 32768;            // auto: chunk buffer of segments larger than one chunk
-constexpr size_t kMaxLds = 160 * 1024;                 // LDS per CU (one workgroup may take all of it)
-#ifndef PM_FINE_THREADS  // A/B builds only: 256 / 1024 measured slower (profiles/r03/sort_fine/fine_threads.jsonl)
-#define PM_FINE_THREADS 512
-#endif
-constexpr int kFineThreads = PM_FINE_THREADS;
-
-struct SortGeom {
-  int FB;    // fine bits
-  int NCB;   // coarse bins per window
-  int nblk;  // point blocks of ppt * kSortThreads points
-  int blk0;  // k_sort_hist: first block of this launch (chunked launches behind a chunked scalar copy)
-  int ppt;   // points per thread, <= kSortPerThread
-  int hsub;  // coarse geometry: histogram blocks per coarse block (bofs rows hold nblk histogram blocks)
-  // words the histogram kernel zeroes for later stages (instead of two
-  // hipMemsetAsync fills per call): the scan sentinel, and the chain-list
-  // counters (4 words) of each window group
-  uint32_t* clr_bh;
-  uint32_t* clr_longs;
-  uint32_t clr_stride;  // words between group headers
-  int clr_groups;
-  // entry index remap of k_sort_coarse (a part of a row table's points, the
-  // split scalar copy): sort-row entry e = j rstride + i -> table index
-  // e + j rdelta + roff (= j npad + c0 + i); rdelta = roff = 0: e itself
-  uint32_t rstride, rdelta, roff;
-};
+// kSortThreads .. kFineThreads and SortGeom: msm_plan.hpp
 
 // signed digit of window w (WinGeom), carry in/out; returns |d| | neg << 31
 // (0 = no contribution).  The top window never carries (scalars < 2^255).
@@ -918,7 +872,6 @@ __device__ __forceinline__ void seg_fold_chunk(const SegChunk<F>& c, bool valid,
   }
 }
 // the sorted lists of one MSM: 1, or the split scalar copy's parts
-constexpr int kMaxParts = 3;
 template <class F>
 struct SegChunks {
   SegChunk<F> c[kMaxParts];
@@ -964,9 +917,7 @@ __global__ void __launch_bounds__(256, 2) k_bucket_seg_q(SegChunks<F> cs, int Wr
 // nsplit = 4).  The result goes out converted to the Rust R = 2^256 layout
 // as host term Q[w * NQ + job] (round 2 folded pairs of bit sums and
 // converted them in a separate k_bits_combine launch, ~19 us per MSM).
-constexpr int kRedThreads = 512;
-constexpr int kTJobs = 2;
-constexpr int kMaxSplit = 64;
+// (kRedThreads, kTJobs, kMaxSplit: msm_plan.hpp)
 // reduce lds[0 .. count) (count a power of two <= kRedThreads; acc = this
 // lane's lds[tid]) into lds[0]; quad-cooperative once 4 s lanes are free
 template <class F>

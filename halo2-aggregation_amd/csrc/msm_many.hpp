@@ -34,8 +34,7 @@
 
 namespace pm {
 
-constexpr uint32_t kManyQuads = 64;          // quads per block (256 threads)
-constexpr uint32_t kManyQuadBudget = 32768;  // quads in flight: ~2 waves per SIMD of the 1024
+// kManyQuads, kManyQuadBudget and many_kq: msm_plan.hpp
 constexpr size_t kManyMappedBytes = size_t(64) << 10;  // host scalars up to this are read from mapped memory
 struct ManyJob {
   uint32_t msm;    // MSM index (output slot)
@@ -296,7 +295,7 @@ int msm_many_impl(Ctx* ctx, const ManyTable* tb, size_t B, const size_t* n, cons
   g.W = tb->W;
   g.H = tb->H;
   g.canonical = (flags & PM_SCALARS_CANONICAL) ? 1u : 0u;
-  g.kq = (uint32_t)std::max<size_t>(1, (total_e + kManyQuadBudget - 1) / kManyQuadBudget);
+  g.kq = many_kq(total_e);
   const size_t per = (size_t)kManyQuads * g.kq;
   std::vector<ManyJob> jobs;
   std::vector<ManyMsm> msms;

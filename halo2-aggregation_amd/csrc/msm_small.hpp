@@ -32,16 +32,10 @@
 
 namespace pm {
 
-constexpr int kSmallWin = 33;          // 4-bit windows of a 128-bit GLV half (+ the carry window)
+// kSmallWin, kSmallQuads, kSmallFusedN and the slice geometry (small_plan): msm_plan.hpp
 constexpr int kSmallMults = 8;         // table entries per base: [1..8] P
 constexpr int kSmallTabPts = 16;       // k_small_table: bases per block (one per quad of each wave)
-constexpr int kSmallQuads = 64;        // k_small_sum: quads per block
 constexpr int kSmallPt = 36;           // an unpacked Xyzz29 in LDS (u32 words)
-// k_small_fused up to here (one slice per window).  Several slices per window
-// (one term per quad, the last block folding) measured slower than table + sum
-// from 64 points on (64 / 128 / 256: 86.6-87.1 / 92.3-93.1 / 95.1-100.8 us
-// against 83.4 / 89.0 / 95.1; profiles/r04/small/fused_ab.jsonl)
-constexpr uint32_t kSmallFusedN = 32;
 
 struct SmallGeom {
   uint32_t n;          // bases

@@ -9,6 +9,7 @@
 
 #include "../../include/pasta_msm.h"
 #include "dropin_digest.hpp"
+#include "msm_plan.hpp"
 #include "quotient_plan.hpp"
 
 #include <condition_variable>
@@ -25,36 +26,16 @@ namespace pm {
 
 int set_error(int code, const std::string& msg);
 
-constexpr int kMinC = 4;
-constexpr int kMaxC = 20;
-// Widest automatic window.  Measured on MI355X (profiles/r01_s2/diag22): once
-// the bucket array (W * 2^(c-1) * 128 B) outgrows the caches, the scattered
-// 128-B bucket stores of k_accumulate dominate: at 2^22, c = 18 took 11.7 ms
-// in accumulate vs 6.1 ms at c = 16; at 2^20, c = 20 took 23.8 ms vs 1.4 ms.
-constexpr int kAutoMaxC = 16;
+// window limits, sort / scan / reduction geometry and the MSM plans: msm_plan.hpp
 constexpr size_t kMaxPoints = size_t(1) << 26;
-// what the host layer needs of the kernels' geometry without their headers
-// (engine.hpp checks both against msm_kernels.hpp): LDS per CU, and the point
-// count a fixed-base table row is padded to a multiple of
-constexpr size_t kLdsPerCu = 160 * 1024;
-constexpr size_t kFixedPad = 8192;
-constexpr int kL1 = 4;  // bucket-segment length of k_bucket_seg_q (one quad per segment)
 // internal msm flag (never in the public header; the C-ABI strips it from
 // caller flags): d_bases already hold the pipeline's R = 2^261 canonical
 // form (resident pm_bases converted at upload), so no per-call conversion
 constexpr uint32_t kBasesR261 = 1u << 30;
-// k_bucket_bits blocks per job = kBitsSplitK / (bucket sets): the bit sums of
-// few sets (row tables, the fixed-base MSM) are split over more blocks; every
-// extra lane also adds one tree addition (round 3 sweep of 4..64 / Wr at
-// 2^19-2^22, profiles/r03/ab/bits_split_sweep.jsonl: 16 best)
-constexpr int kBitsSplitK = 16;
 // drop-in base cache of pm_msm / pm_msm_ctx (capi_dropin.hip): base sets of at least
 // kDropinMinN points are kept resident, keyed by a content digest; at most
 // kDropinEntries sets and kDropinBytes of device memory per context
 constexpr size_t kDropinMinN = size_t(1) << 12;
-// the split scalar copy of row-table MSMs with host scalars (engine.hpp)
-constexpr size_t kSplitCopyMinN = PM_SPLIT_COPY_MIN_N;
-constexpr size_t kSplitCopy3MinN = size_t(1) << 21;  // three parts from here (measured at 2^20 and 2^22)
 constexpr int kDropinEntries = 4;
 constexpr size_t kDropinBytes = size_t(16) << 30;
 // ... and at most this fraction (1/kDropinFreeDiv) of the device memory free
@@ -130,27 +111,6 @@ struct CachedUpload {
   int put(const std::vector<T>& v, hipStream_t st, size_t pad = 0);
 };
 
-struct MsmPlan {
-  int c;          // target window width (bits)
-  int W;          // windows = ceil(256 / c); widths base or base+1 (WinGeom)
-  int base, extra;
-  int cmax;       // widest window
-  int K;          // max |digit| = 2^(cmax-1)
-  int L1;         // bucket-segment length of k_bucket_seg_q
-  int log2L1;
-  int NB;         // bucket slots per window (K+1 rounded up to L1)
-  int M1;         // segments per window: K / L1 (slots [0, K); bucket K apart)
-  int NB2;        // bits of the segment index
-  uint32_t n;
-  uint32_t chunk;     // sorted entries per accumulate lane
-  uint32_t nthreads;  // accumulate lanes
-  int width(int w) const { return base + (w < extra ? 1 : 0); }
-};
-
-MsmPlan make_plan(size_t n, int c_override, int min_chunk = 0);
-// fixed-base MSM over a table of npad rows per window (accumulate work =
-// W * npad entries)
-MsmPlan make_plan_fixed(size_t npad, int c, int min_chunk = 0);
 // fixed-base windows: one bucket set of 2^(c-1) buckets
 constexpr int kFixedMaxC = 20;
 constexpr int kAutoFixedC = 16;       // n <= 2^21
@@ -250,20 +210,16 @@ struct ManyTable {
   size_t n = 0;
   uint32_t c = 0, W = 0, H = 0;
 };
-// geometry for a prefix of n bases: the widest window (fewest additions per
-// scalar, W(c) of them) whose table fits kManyTabBudget; c = 4 up to the hard
-// cap, beyond it pm_msm_resident_many falls back to one resident MSM each.
-// W(c): signed digits in [-(2^(c-1) - 1), 2^(c-1)] of a scalar < 2^255 need a
-// carry window only when c divides 255.
+// (the table geometry of a prefix of n bases, many_pick_c: msm_plan.hpp)
+// The table budget and cap as tests/msm_short_edge_util.py (many_budget) reads them from this
+// file's text: the GPU edge tests size their base prefixes by it, and it keeps reading them
+// where it always has.  The plan's own definitions are msm_plan.hpp's; the two cannot differ.
+namespace as_read_by_tests {
 constexpr size_t kManyTabBudget = size_t(2) << 30;
 constexpr size_t kManyTabCap = size_t(8) << 30;
-inline uint32_t many_windows(uint32_t c) { return 255u % c == 0 ? 255u / c + 1u : (255u + c - 1u) / c; }
-inline size_t many_bytes_per_base(uint32_t c) { return (size_t)many_windows(c) << (c - 1) << 7; }
-inline uint32_t many_pick_c(size_t n) {
-  for (uint32_t c = 8; c > 4; c--)
-    if (n * many_bytes_per_base(c) <= kManyTabBudget) return c;
-  return 4;
-}
+}  // namespace as_read_by_tests
+static_assert(as_read_by_tests::kManyTabBudget == kManyTabBudget && as_read_by_tests::kManyTabCap == kManyTabCap,
+              "runtime.hpp restates msm_plan.hpp's many-MSM table limits");
 constexpr size_t kNttTwiddleSlots = 4;
 constexpr uint32_t kNttMaxLog = 28;  // pm_fft: three passes above 2^22; BN254 Fr has 2-adicity 28
 // polynomial openings (poly_engine.hpp)

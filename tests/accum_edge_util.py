@@ -13,7 +13,7 @@ the C port.  pm_accum_batch_proofs from bytes is OUT OF SCOPE for the planted
 relations: its challenges are hashed from the points, so no coefficient can be
 chosen (its points still reach the same kernels).
 
-term_plan restates acc_terms and the pairing loop of accum_engine.hpp: the f
+term_plan restates acc_terms and its pairing loop (accum_plan.hpp): the f
 slots (one per distinct commitment in first-use order over the rotation sets
 in ascending order), the h_i, W_0..W_{S-1} for w and again for zw, g1; with
 each term's output, source and integer coefficient, and the (t, t + 1) pairs
@@ -26,7 +26,7 @@ negative half.  naf_digits restates naf128: digit i = bit i+1 of 3 k minus bit
 i+1 of k, 128 positions.  deal() is k_acc_termadd's round-robin: the nonzero
 digits of k1 in ascending position, then k2's, rank n to lane n mod S.
 
-acc_path restates the thresholds of accum_device_impl from kAccLaneBudget and
+acc_path restates the thresholds of accum_plan.hpp acc_path from kAccLaneBudget and
 kAccSumLanes as parsed from the header, so a test can assert the path it means
 to hit and fails when a threshold moves.
 
@@ -201,7 +201,7 @@ def engine_constants(path=ENGINE_HDR):
 
 
 def acc_path(B, T, Tp, npair, split=-1, tpl=-1):
-    """accum_device_impl's choices -> dict(lgS, quad_terms, tpl (0 in the split
+    """accum_plan.hpp acc_path's choices -> dict(lgS, quad_terms, tpl (0 in the split
     form), pstep, lgL)."""
     k = engine_constants()
     budget, sumlanes = k["kAccLaneBudget"], k["kAccSumLanes"]

@@ -45,7 +45,7 @@ import msm_ref
 import pasta as P
 
 M64 = (1 << 64) - 1
-SORT_THREADS = 1024       # msm_kernels.hpp kSortThreads
+SORT_THREADS = 1024       # msm_plan.hpp kSortThreads
 SORT_PER_THREAD = 8       # kSortPerThread
 SORT_B = SORT_THREADS * SORT_PER_THREAD   # kSortB: fixed-base padding, part rounding
 SPLIT_COPY_MIN_N = 1 << 18    # PM_SPLIT_COPY_MIN_N
@@ -213,7 +213,7 @@ def _rnd(v):
 
 
 def part_starts(n, split):
-    """pstart[] of engine.hpp: one part, or (split: host scalars on a row
+    """pstart[] of msm_plan.hpp msm_parts: one part, or (split: host scalars on a row
     table) 3/8 + 5/8 from 2^18 points, 1/4 + 3/8 + 3/8 from 2^21."""
     if not split or n < SPLIT_COPY_MIN_N:
         return [0, n]
@@ -223,8 +223,8 @@ def part_starts(n, split):
 
 
 def sort_ppt(stride):
-    """Points per sort thread of a digit row of `stride` points (engine.hpp
-    geom(): the largest power of two <= 8 that leaves >= 128 blocks)."""
+    """Points per sort thread of a digit row of `stride` points (msm_plan.hpp
+    sort_plan: the largest power of two <= 8 that leaves >= 128 blocks)."""
     ppt = 1
     while ppt < SORT_PER_THREAD and stride >= 256 * ppt * SORT_THREADS:
         ppt *= 2
@@ -233,7 +233,7 @@ def sort_ppt(stride):
 
 def sort_block(stride):
     """Points per histogram block of that row: ppt x 1024, halved when the
-    row has 128 <= blocks < 256 (hsub in geom())."""
+    row has 128 <= blocks < 256 (hsub in sort_plan)."""
     ppt = sort_ppt(stride)
     nblk = (stride + ppt * SORT_THREADS - 1) // (ppt * SORT_THREADS)
     hsub = 2 if ppt >= 2 and 128 <= nblk < 256 else 1

@@ -100,13 +100,15 @@ RUNTIME_HDR = os.path.join(os.path.dirname(GLV_HDR), "runtime.hpp")
 GLV_CURVES = {"PallasCurve": P.PALLAS, "VestaCurve": P.VESTA, "Bn254Curve": P.BN254}
 _GLV_NAME = {0: "PallasCurve", 1: "VestaCurve", 2: "Bn254Curve"}
 
-SMALL_WIN = 33        # msm_small.hpp kSmallWin
+SMALL_WIN = 33        # msm_plan.hpp kSmallWin
 SMALL_FUSED_N = 32    # kSmallFusedN
 SMALL_QUADS = 64      # kSmallQuads
-SMALL_SLICES = 8      # engine.hpp msm_small_impl kSmallSlices
-SMALL_LANES_T = 4096  # 2 n from which k_small_sum_lanes runs
-MANY_QUADS = 64       # msm_many.hpp kManyQuads
+SMALL_SLICES = 8      # kSmallSlices
+SMALL_LANES_T = 4096  # kSmallLanesT: 2 n from which k_small_sum_lanes runs
+MANY_QUADS = 64       # kManyQuads
 MANY_QUAD_BUDGET = 32768   # kManyQuadBudget
+# many-MSM base prefix -> window width of the GPU tests
+MANY_PREFIX = ((4096, 8), (6000, 7), (8192, 6), (16384, 5), (32768, 4))
 TOP_NIBBLE_MAX = {0: 6, 1: 6, 2: 3}
 
 
@@ -228,7 +230,7 @@ def many_windows(c):
 
 
 def many_geom(c):
-    """(W, H) of runtime.hpp many_windows(c) and the largest digit 2^(c-1)."""
+    """(W, H) of msm_plan.hpp many_windows(c) and the largest digit 2^(c-1)."""
     return many_windows(c), 1 << (c - 1)
 
 
@@ -237,7 +239,7 @@ def many_bytes_per_base(c):
 
 
 def many_budget(path=RUNTIME_HDR):
-    """(kManyTabBudget, kManyTabCap) read from runtime.hpp."""
+    """(kManyTabBudget, kManyTabCap) read from runtime.hpp (held equal to msm_plan.hpp's there)."""
     txt = open(path).read()
     v = {}
     for nm in ("kManyTabBudget", "kManyTabCap"):
@@ -316,7 +318,7 @@ def many_special_scalars(curve, c):
 
 
 def many_kq(ns, c):
-    """kq of msm_many_impl for a call of MSM lengths ns."""
+    """kq of msm_many_impl (msm_plan.hpp many_kq) for a call of MSM lengths ns."""
     return max(1, -(-sum(ns) * many_windows(c) // MANY_QUAD_BUDGET))
 
 
@@ -334,7 +336,7 @@ def many_quad_starts(ns, c):
 
 # ----------------------------------------------------------- small-MSM geometry
 def small_geom(n):
-    """(path, kq, ns) of msm_small_impl: "fused" (n <= 32: one term per quad),
+    """(path, kq, ns) of msm_small_impl (msm_plan.hpp small_plan): "fused" (n <= 32: one term per quad),
     "quads" or "lanes" (2 n >= 4096)."""
     T = 2 * n
     if n <= SMALL_FUSED_N:

@@ -15,7 +15,12 @@
 //                   valid shapes and on malformed ones (out-of-range query
 //                   indices, unterminated or overflowing expression code, null
 //                   arrays), which must be rejected without reading out of
-//                   bounds.
+//                   bounds;
+//   * msm_plan.hpp  the MSM drivers' host plans over n = 2^k, 2^k +- 1, every
+//                   window, raw and table schedules: the split copy's parts
+//                   ascend on kSortB boundaries, the sort kernels' LDS requests
+//                   fit a CU, the accumulate lanes and scan blocks cover their
+//                   work.
 // Exit status 0 = every check passed (a sanitizer report aborts first).
 #include <algorithm>
 #include <cstdio>
@@ -27,6 +32,7 @@
 #include "../../halo2-aggregation_amd/csrc/accum_plan.hpp"
 #include "../../halo2-aggregation_amd/csrc/blake2b.hpp"
 #include "../../halo2-aggregation_amd/csrc/host_ec.hpp"
+#include "../../halo2-aggregation_amd/csrc/msm_plan.hpp"
 
 using namespace pm;
 
@@ -276,6 +282,78 @@ static void plan_checks() {
   CHECK(!acc_validate(nullptr, q, L, nullptr).empty());
 }
 
+// invariants of one call's schedule (msm_plan.hpp msm_schedule)
+static void schedule_checks(const MsmShape& sh) {
+  const MsmSchedule s = msm_schedule(sh);
+  CHECK(s.err == kPlanOk);
+  const MsmParts& p = s.parts;
+  CHECK(p.nch >= 1 && p.nch <= kMaxParts && p.pstart[0] == 0 && p.pstart[p.nch] == sh.n);
+  for (int ch = 0; ch < p.nch; ch++) {
+    CHECK(p.pstart[ch] < p.pstart[ch + 1]);  // parts ascend
+    CHECK(p.pstart[ch + 1] % kSortB == 0 || p.pstart[ch + 1] == sh.n);
+    const SortPlan& q = s.part[ch];
+    CHECK(q.c0 == p.pstart[ch] && q.c0 + q.nc == p.pstart[ch + 1] && q.nc <= q.stride);
+    CHECK(q.lds_coarse <= kMaxLds && q.lds_fine <= kMaxLds);
+    CHECK(q.chn >= 64 && q.chn <= q.cache_n);
+    CHECK((size_t)q.nthreads * q.chunk >= q.nW);                      // the accumulate lanes cover the entries
+    CHECK((size_t)q.nb * q.tiles.chunk >= q.TOTB);                    // the scan blocks cover the counters
+    CHECK((size_t)q.g.nblk * q.g.ppt * kSortThreads >= q.stride);     // the histogram blocks cover the row
+    CHECK(q.g.ppt >= 1 && q.gm.ppt <= kSortPerThread && q.gm.ppt == q.g.ppt * q.gm.hsub);
+    CHECK(q.gm.nblk == q.g.nblk * s.kmerge && q.gm.nblk % q.gm.hsub == 0);
+    CHECK(p.nch == 1 || (size_t)q.gm.roff + q.gm.rstride + q.gm.rdelta == q.c0 + sh.npad);
+  }
+  CHECK(s.red.Wr * s.kmerge == s.pl.W && s.red.NQ == s.pl.NB2 + kTJobs + 1);
+  CHECK(s.red.nsplit >= 1 && s.red.nsplit <= kMaxSplit);
+  CHECK((size_t)s.red.seg_blocks * 256 >= 4ull * s.red.Wr * s.pl.M1);
+}
+
+static void msm_plan_checks() {
+  std::vector<size_t> ns;
+  for (int k = 0; k <= 26; k++)
+    for (int d = -1; d <= 1; d++) {
+      const long long v = (1ll << k) + d;
+      if (v >= 1 && v <= (1ll << 26)) ns.push_back((size_t)v);
+    }
+  for (size_t v : {(size_t(1) << 18) + 11, (size_t(1) << 21) + 77, (size_t(1) << 22) + 3, kSplitCopyMinN - 1,
+                   kSplitCopyMinN, kSplitCopyMinN + 1})
+    ns.push_back(v);
+  const int fine_kb[4][2] = {{0, 0}, {8, 8}, {128, 32}, {160, 160}};  // PM_FINE_CACHE_KB / PM_FINE_CHUNK_KB
+  for (size_t n : ns)
+    for (int c = kMinC - 1; c <= kMaxC; c++) {  // kMinC - 1 stands for the automatic window
+      const int wc = c < kMinC ? 0 : c;
+      for (const auto& kb : fine_kb) {
+        MsmShape sh{};
+        sh.n = n;
+        sh.rows = 1;
+        sh.window_c = wc;
+        sh.split_copy = -1;
+        sh.fine_cache_kb = kb[0];
+        sh.fine_chunk_kb = kb[1];
+        schedule_checks(sh);  // the raw pipeline
+        if (!wc) continue;
+        const int W = make_plan_fixed(kSortB, wc).W;
+        for (int rows : {1, W})
+          for (int host = 0; host < 2; host++) {
+            sh.fixed = true;
+            sh.npad = std::max<size_t>(kSortB, sort_round(n));
+            sh.fixed_c = wc;
+            sh.rows = rows;
+            sh.host_scalars = host != 0;
+            schedule_checks(sh);  // a table, one part or the split copy's
+          }
+      }
+    }
+  for (size_t n : ns) {
+    if (n > PM_SMALL_MSM_LIMIT) continue;
+    const SmallPlan p = small_plan(n);
+    const size_t per = p.fused || !p.lanes ? (size_t)kSmallQuads : 256;
+    CHECK(p.kq >= 1 && p.ns >= 1 && per * p.kq * p.ns >= 2 * n);  // the slices cover the 2 n terms
+    CHECK(p.fused || p.ns <= kSmallSlices);
+  }
+  for (uint32_t c = 4; c <= 8; c++) CHECK(many_windows(c) * c >= 255 && (many_windows(c) - 1) * c <= 255);
+  for (size_t n : ns) CHECK(many_pick_c(n) == 4 || n * many_bytes_per_base(many_pick_c(n)) <= kManyTabBudget);
+}
+
 int main() {
   field_checks<PallasFp>(2000);
   field_checks<VestaFp>(2000);
@@ -285,6 +363,7 @@ int main() {
   horner_checks<Bn254Fq>(false);
   blake2b_checks();
   plan_checks();
+  msm_plan_checks();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

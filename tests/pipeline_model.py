@@ -1,6 +1,6 @@
 """Host-logic model of the HIP MSM pipeline (test helper).
 
-Mirrors halo2-aggregation_amd/csrc/{capi_ctx.hip:make_plan, msm_kernels.hpp} step
+Mirrors halo2-aggregation_amd/csrc/{msm_plan.hpp:make_plan, msm_kernels.hpp} step
 by step, but over the additive group Z_r (a point is replaced by its discrete
 log, point addition by integer addition mod r).  It lets the CPU test-suite
 check the design's algebra -- signed digits, counting sort, slice ownership +
@@ -28,7 +28,7 @@ def make_plan(n, c_override=0, chunk_override=0):
     NB = ((K + 1 + L1 - 1) // L1) * L1
     M1 = K // L1  # segments cover slots [0, K); bucket K is a host term of its own
     NB2 = bit_length(M1 - 1)
-    work = n * W  # one window group (capi_ctx.hip make_plan)
+    work = n * W  # one window group (msm_plan.hpp make_plan)
     target = 256 * 1024
     chunk = max(16, (work + target - 1) // target)
     if chunk_override:
@@ -64,7 +64,7 @@ def digits(s, W):
     return out
 
 
-K_TJOBS = 2  # msm_kernels.hpp kTJobs
+K_TJOBS = 2  # msm_plan.hpp kTJobs
 
 
 def msm_model(scalars, dlogs, r, c_override=0, chunk_override=0):

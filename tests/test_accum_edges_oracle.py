@@ -13,6 +13,7 @@ import accum_edge_util as X
 import accum_ref as R
 import accum_util as U
 import pasta as P
+import plan_native as N
 from msm_short_edge_util import glv_model
 
 CURVES = (0, 1, 2)
@@ -130,12 +131,29 @@ def test_corner_halves_stay_below_2_127(cid):
         assert top == 0
 
 
-def test_path_constants():
+@pytest.fixture(scope="module")
+def plan_exe(tmp_path_factory):
+    return N.build(tmp_path_factory)
+
+
+def test_path_constants(plan_exe):
     """acc_path on the header's constants: the batch sizes of every lgL, the
-    quad form of the term additions and the automatic two-term lanes."""
+    quad form of the term additions and the automatic two-term lanes; the
+    constants and the same paths asked of the product's acc_path
+    (tests/native/plan_dump.cpp over csrc/accum_plan.hpp)."""
     k = X.engine_constants()
     assert k == {"kAccLaneBudget": 1024 * 2 * 64, "kAccSumLanes": 16384}
+    kc = N.ask1(plan_exe, "consts")
+    assert {nm: kc[nm] for nm in k} == k
     T, Tp, npair = 30, 21, 16
+
+    def native(B, split=-1, tpl=-1):
+        g = N.ask1(plan_exe, "acc %d %d %d %d %d %d -1" % (B, T, Tp, npair, split, tpl))
+        return dict(lgS=g["lgS"], quad_terms=bool(g["quad_terms"]), tpl=g["tpl"], pstep=g["pstep"], lgL=g["lgL"])
+
+    for B in (8193, 4097, 2049, 257, 129, 1, 34, 35, 3000):
+        assert native(B) == X.acc_path(B, T, Tp, npair), B
+    assert native(8, split=0, tpl=2) == X.acc_path(8, T, Tp, npair, split=0, tpl=2)
     assert [X.batch_for_lgL(lg, T, Tp, npair) for lg in range(6)] == [8193, 4097, 2049, 257, 129, 1]
     assert X.acc_path(34, T, Tp, npair)["quad_terms"] and not X.acc_path(35, T, Tp, npair)["quad_terms"]
     assert X.acc_path(3000, T, Tp, npair) == dict(lgS=0, quad_terms=False, tpl=2, pstep=2, lgL=2)

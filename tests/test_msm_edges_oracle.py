@@ -19,6 +19,7 @@ import pytest
 import msm_edge_util as E
 import msm_ref
 import pasta as P
+import plan_native as N
 
 # (c, rows) of the GPU paths; a fixed table keeps one row per window
 WIDTHS = ((16, 8), (16, 4), (16, 2), (16, 16), (20, 13), (16, 1), (20, 1), (13, 1), (12, 1))
@@ -147,13 +148,32 @@ def test_c_port_large(curve):
     assert _c_point(curve, S, B) == E.expected_by_dlog(curve, S, D)
 
 
-def test_boundaries_follow_engine():
-    """part_starts / sort_block restate engine.hpp (pstart[], geom())."""
+@pytest.fixture(scope="module")
+def plan_exe(tmp_path_factory):
+    return N.build(tmp_path_factory)
+
+
+def test_boundaries_follow_engine(plan_exe):
+    """part_starts / sort_block restate csrc/msm_plan.hpp (msm_parts, sort_plan),
+    asked through tests/native/plan_dump.cpp."""
+    def parts(n, split):   # a row table, host scalars (the split copy) or device scalars
+        return N.ask1(plan_exe, "parts %d 1 %d -1" % (n, 1 if split else 0))["pstart"]
+
+    def block(stride):     # (points per coarse thread, points per histogram block) of a raw row
+        g = N.ask1(plan_exe, "sort %d 0 0 0 1 0 -1 0 0" % stride)
+        return g["p0_gm_ppt"], g["p0_g_ppt"] * k["kSortThreads"]
+
+    k = N.ask1(plan_exe, "consts")
+    assert (k["kSortThreads"], k["kSortPerThread"], k["kSortB"]) == (E.SORT_THREADS, E.SORT_PER_THREAD, E.SORT_B)
+    assert (k["kSplitCopyMinN"], k["kSplitCopy3MinN"]) == (E.SPLIT_COPY_MIN_N, E.SPLIT_COPY3_MIN_N)
     n = (1 << 18) + 11
     assert E.part_starts(n, True) == [0, 106496, n] and E.part_starts(n, False) == [0, n]
-    assert E.part_starts((1 << 18) - 1, True) == [0, (1 << 18) - 1]
+    assert parts(n, True) == [0, 106496, n] and parts(n, False) == [0, n]
+    assert E.part_starts((1 << 18) - 1, True) == [0, (1 << 18) - 1] == parts((1 << 18) - 1, True)
     m = (1 << 22) + 3
-    assert E.part_starts(m, True) == [0, 1048576, 2621440 + 8192, m]
+    assert E.part_starts(m, True) == [0, 1048576, 2621440 + 8192, m] == parts(m, True)
+    for s in ((1 << 14) + 5, (1 << 18) - 1, (1 << 18) + 5, 1 << 19, 1 << 20, 1 << 22, (1 << 22) + 3):
+        assert block(s) == (E.sort_ppt(s), E.sort_block(s)), s
     assert E.sort_ppt((1 << 14) + 5) == 1 and E.sort_ppt((1 << 18) - 1) == 1 and E.sort_ppt((1 << 18) + 5) == 2
     assert E.sort_ppt(1 << 19) == 4 and E.sort_ppt(1 << 20) == 8 and E.sort_ppt(1 << 22) == 8
     assert E.sort_block(1 << 20) == 4096      # 128 blocks of 8192 points: histogram blocks split in two

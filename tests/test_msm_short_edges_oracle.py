@@ -18,9 +18,7 @@ GPU sees these inputs:
   sources.
 """
 import math
-import os
 import random
-import re
 
 import numpy as np
 import pytest
@@ -29,11 +27,10 @@ import msm_edge_util as E
 import msm_ref
 import msm_short_edge_util as U
 import pasta as P
+import plan_native as N
 
-CSRC = os.path.dirname(U.GLV_HDR)
 SMALL_N = (("fused", 32), ("quads", 300), ("lanes", 2048))
-# prefix -> window width of the GPU tests
-MANY_PREFIX = ((4096, 8), (6000, 7), (8192, 6), (16384, 5), (32768, 4))
+MANY_PREFIX = U.MANY_PREFIX
 _CACHE = {}
 
 
@@ -335,13 +332,22 @@ def test_many_digit_patterns_hold_what_they_claim(curve, c):
         assert s != sp["pattern:" + k]
 
 
-def test_many_batches_and_thresholds():
-    """The geometry the GPU tests rely on, restated from the sources."""
+@pytest.fixture(scope="module")
+def plan_exe(tmp_path_factory):
+    return N.build(tmp_path_factory)
+
+
+def test_many_batches_and_thresholds(plan_exe):
+    """The geometry the GPU tests rely on, asked of the product's plan code
+    (tests/native/plan_dump.cpp over csrc/msm_plan.hpp)."""
     budget, cap = U.many_budget()
     assert (budget, cap) == (2 << 30, 8 << 30)
-    txt = open(os.path.join(CSRC, "runtime.hpp")).read()
-    assert "255u % c == 0 ? 255u / c + 1u : (255u + c - 1u) / c" in txt
-    assert "(size_t)many_windows(c) << (c - 1) << 7" in txt
+    k = N.ask1(plan_exe, "consts")
+    assert (k["kManyTabBudget"], k["kManyTabCap"]) == (budget, cap)
+    for c, g in zip(range(1, 21), N.ask(plan_exe, ("manyc %d" % c for c in range(1, 21)))):
+        # a carry window only when c divides 255; 128-B entries, 2^(c-1) per window
+        assert g["W"] == (255 // c + 1 if 255 % c == 0 else (255 + c - 1) // c) == U.many_windows(c)
+        assert g["bytes_per_base"] == g["W"] << (c - 1) << 7 == U.many_bytes_per_base(c)
     # many_pick_c: the widest window whose table fits the budget
     for c in (8, 7, 6, 5):
         top = budget // U.many_bytes_per_base(c)
@@ -349,15 +355,17 @@ def test_many_batches_and_thresholds():
     assert [budget // U.many_bytes_per_base(c) for c in (8, 7, 6, 5)] == [4096, 7084, 12192, 20164]
     assert [U.many_pick_c(n) for n, _ in MANY_PREFIX] == [c for _, c in MANY_PREFIX]
     assert [U.many_pick_c(n) for n in (6000, 8192, 16384, 32768)] == [7, 6, 5, 4]
+    tops = [t + d for t in (4096, 7084, 12192, 20164) for d in (0, 1)]
+    assert [g["c"] for g in N.ask(plan_exe, ("many %d" % n for n in tops))] == [8, 7, 7, 6, 6, 5, 5, 4]
+    assert [g["c"] for g in N.ask(plan_exe, ("many %d" % n for n, _ in MANY_PREFIX))] == [c for _, c in MANY_PREFIX]
     assert cap // U.many_bytes_per_base(4) == 131072      # one base more: no table, the fallback
-    many = open(os.path.join(CSRC, "msm_many.hpp")).read()
-    assert re.search(r"kManyQuads = (\d+)", many).group(1) == str(U.MANY_QUADS)
-    assert re.search(r"kManyQuadBudget = (\d+)", many).group(1) == str(U.MANY_QUAD_BUDGET)
+    assert (k["kManyQuads"], k["kManyQuadBudget"]) == (U.MANY_QUADS, U.MANY_QUAD_BUDGET)
     for nb, c in MANY_PREFIX:
         W = U.many_geom(c)[0]
         for big in (False, True):
             ns, offs = U.many_batch(nb, c, big)
             kq = U.many_kq(ns, c)
+            assert N.ask1(plan_exe, "manykq %d" % (sum(ns) * W))["kq"] == kq
             assert min(ns) == 1 and 500 <= max(ns) <= 600 or not big
             assert offs[-1] + ns[-1] == nb                       # the last base of the prefix
             iv = sorted(zip(offs, ns))
@@ -371,19 +379,22 @@ def test_many_batches_and_thresholds():
                 assert kq == 1 and sum(ns) * W <= U.MANY_QUAD_BUDGET
 
 
-def test_small_path_geometry():
-    small = open(os.path.join(CSRC, "msm_small.hpp")).read()
-    eng = open(os.path.join(CSRC, "engine.hpp")).read()
-    assert re.search(r"kSmallWin = (\d+)", small).group(1) == str(U.SMALL_WIN)
-    assert re.search(r"kSmallFusedN = (\d+)", small).group(1) == str(U.SMALL_FUSED_N)
-    assert re.search(r"kSmallQuads = (\d+)", small).group(1) == str(U.SMALL_QUADS)
-    assert re.search(r"kSmallSlices = (\d+)", eng).group(1) == str(U.SMALL_SLICES)
-    assert "lanes = T >= %du" % U.SMALL_LANES_T in eng
+def test_small_path_geometry(plan_exe):
+    k = N.ask1(plan_exe, "consts")
+    assert k["kSmallWin"] == U.SMALL_WIN
+    assert k["kSmallFusedN"] == U.SMALL_FUSED_N
+    assert k["kSmallQuads"] == U.SMALL_QUADS
+    assert k["kSmallSlices"] == U.SMALL_SLICES
+    assert k["kSmallLanesT"] == U.SMALL_LANES_T   # lanes = T >= 4096
+    lanes_from = U.SMALL_LANES_T // 2            # the first n whose 2 n terms run k_small_sum_lanes
+    assert [g["path"] for g in N.ask(plan_exe, ("small %d" % n for n in (lanes_from - 1, lanes_from)))] == \
+        ["quads", "lanes"]
     want = {1: ("fused", 1, 1), 2: ("fused", 1, 1), 16: ("fused", 1, 1), 17: ("fused", 1, 1), 32: ("fused", 1, 1),
             33: ("quads", 1, 2), 300: ("quads", 2, 5), 2047: ("quads", 8, 8), 2048: ("lanes", 2, 8),
             4097: ("lanes", 5, 7)}
-    for n, g in want.items():
+    for (n, g), d in zip(want.items(), N.ask(plan_exe, ("small %d" % n for n in want))):
         assert U.small_geom(n) == g, n
+        assert (d["path"], d["kq"], d["ns"]) == g, n
 
 
 # ---------------------------------------- the planted collisions are reached
