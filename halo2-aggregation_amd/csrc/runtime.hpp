@@ -321,6 +321,8 @@ struct pm_ctx {
   pm::Buf dom_ptrs;
   // quotient numerator (quotient_engine.hpp): the call's pointer table and constants
   pm::Buf quot_io;
+  // pairing decider (pairing_engine.hpp): per item the two G1 points in the kernels' form and a flag word
+  pm::Buf pair_io;
   // the power table of the last omega a grand product named: one prover calls with one omega, and the
   // table's chain of squarings is pure latency (0.04 ms of a 2^20 call); valid while gp_tab.gen == gp_tab_gen
   pm::Buf gp_tab;

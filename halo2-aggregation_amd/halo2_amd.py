@@ -42,6 +42,7 @@ ACCUM_CURVES = (PALLAS, VESTA, BN254)
 # per-proof status bits of the proof-byte entries (pm_*_proofs*)
 PROOF_BAD_POINT = 8
 PROOF_BAD_SCALAR = 16
+DECIDE_NOT_ON_CURVE = 8  # PM_DECIDE_NOT_ON_CURVE
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
@@ -384,6 +385,13 @@ def _load():
                                   ctypes.c_int),
         "pm_accum_batch_proofs_device": ([_vp, ctypes.c_int, ctypes.POINTER(PmProofShape), ctypes.c_size_t, _u64p,
                                           _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "pm_pairing_create": ([_vp, _u64p, _u64p, ctypes.POINTER(_vp)], ctypes.c_int),
+        "pm_pairing_info": ([_vp, _u32p, _szp, _u32p], ctypes.c_int),
+        "pm_pairing_release": ([_vp], ctypes.c_int),
+        "pm_pairing_check_device": ([_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "pm_accum_decide_device": ([_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+        "pm_accum_decide": ([_vp, _vp, ctypes.c_size_t, _u64p, _u32p, _u32p, _u32p, _u64p], ctypes.c_int),
+        "pm_accum_decide_host": ([_vp, ctypes.c_size_t, _u64p, _u32p, _u32p, _u32p, _u64p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if not hasattr(L, name) and os.environ.get("PM_LIB"):
@@ -687,6 +695,67 @@ class Quotient:
             self.release()
         except Exception:
             pass
+
+
+class Pairing:
+    """pm_pairing: the decider's two fixed G2 arguments (ParamsVerifier's g2 and
+    s_g2 = [tau]G2), checked on the host, with the line tables of both Miller
+    loops.  g2, s_g2: (16,) u64 = x.c0, x.c1, y.c0, y.c1, Montgomery R = 2^256.
+    ctx=None gives a host-only object (accum_decide_host)."""
+
+    def __init__(self, ctx, g2, s_g2):
+        self.h = None
+        a = np.ascontiguousarray(g2, dtype=np.uint64).reshape(-1)
+        b = np.ascontiguousarray(s_g2, dtype=np.uint64).reshape(-1)
+        if a.shape[0] != 16 or b.shape[0] != 16:
+            raise ValueError("a G2 point is 16 x u64 (x.c0, x.c1, y.c0, y.c1)")
+        h = _vp()
+        _check(lib().pm_pairing_create(ctx.h if ctx is not None else None, _p(a), _p(b), ctypes.byref(h)))
+        self.h = h
+
+    def info(self):
+        """dict: steps (line evaluations per pairing), table_bytes, lanes_per_pairing"""
+        st, ln, tb = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_size_t(0)
+        _check(lib().pm_pairing_info(self.h, ctypes.byref(st), ctypes.byref(tb), ctypes.byref(ln)))
+        return dict(steps=st.value, table_bytes=tb.value, lanes_per_pairing=ln.value)
+
+    def release(self):
+        if self.h is not None:
+            lib().pm_pairing_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _decide_args(quads, status_in, want_gt):
+    q = np.ascontiguousarray(quads, dtype=np.uint64).reshape(-1, 4, 8)
+    B = q.shape[0]
+    si = None
+    if status_in is not None:
+        si = np.ascontiguousarray(status_in, dtype=np.uint32).reshape(-1)
+        if si.shape[0] != B:
+            raise ValueError("status_in holds one word per quad")
+    ok = np.zeros(B, dtype=np.uint32)
+    st = np.zeros(B, dtype=np.uint32)
+    gt = np.zeros((B, 12, 4), dtype=np.uint64) if want_gt else None
+    return q, B, si, ok, st, gt
+
+
+def _u32(a):
+    return a.ctypes.data_as(_u32p) if a is not None else None
+
+
+def accum_decide_host(pairing: Pairing, quads, status_in=None, want_gt=False):
+    """pm_accum_decide_host: ok = [e(w, s_g2) e(-(zw + f + e), g2) == 1] per quad on the CPU
+    (no device, no context).  quads (B, 4, 8) u64 -> (ok (B,) u32, status (B,) u32[, gt (B, 12, 4)])."""
+    q, B, si, ok, st, gt = _decide_args(quads, status_in, want_gt)
+    _check(lib().pm_accum_decide_host(pairing.h, B, _p(q), _u32(si), _u32(ok), _u32(st),
+                                      _p(gt) if want_gt else None))
+    return (ok, st, gt) if want_gt else (ok, st)
 
 
 def quotient_eval_host(shape: ProofShape, scalars, x, challenges):
@@ -1033,6 +1102,36 @@ class Context:
         _check(lib().pm_accum_batch_proofs_device(self.h, shape.curve, ctypes.byref(shape.c), B, _p(vk),
                                                   _vp(d_proofs), stride, _vp(d_inst or None), _vp(d_challenges),
                                                   _vp(d_quads), _vp(d_h or None), _vp(d_status or None)))
+
+    def pairing(self, g2, s_g2):
+        return Pairing(self, g2, s_g2)
+
+    def pairing_check_device(self, pairing: Pairing, B, d_pairs, d_ok, d_status_in=0, d_status=0, d_gt=0):
+        """pm_pairing_check_device: ok = [e(A, s_g2) e(C, g2) == 1]; d_pairs B x 2 x 8 u64."""
+        _check(lib().pm_pairing_check_device(self.h, pairing.h, B, _vp(d_pairs), _vp(d_status_in or None), _vp(d_ok),
+                                             _vp(d_status or None), _vp(d_gt or None)))
+
+    def accum_decide_device(self, pairing: Pairing, B, d_quads, d_ok, d_status_in=0, d_status=0, d_gt=0):
+        """pm_accum_decide_device: the decider on B accumulator quads (device pointers)."""
+        _check(lib().pm_accum_decide_device(self.h, pairing.h, B, _vp(d_quads), _vp(d_status_in or None), _vp(d_ok),
+                                            _vp(d_status or None), _vp(d_gt or None)))
+
+    def accum_decide(self, pairing: Pairing, quads, status_in=None, want_gt=False):
+        """pm_accum_decide: host arrays in and out -> (ok, status[, gt]) as accum_decide_host."""
+        q, B, si, ok, st, gt = _decide_args(quads, status_in, want_gt)
+        _check(lib().pm_accum_decide(self.h, pairing.h, B, _p(q), _u32(si), _u32(ok), _u32(st),
+                                     _p(gt) if want_gt else None))
+        return (ok, st, gt) if want_gt else (ok, st)
+
+    def verify_proofs_device(self, shape: ProofShape, pairing: Pairing, B, vk_repr, d_proofs, stride, d_inst,
+                             d_challenges, d_quads, d_status, d_ok, d_h=0, d_gt=0):
+        """pm_accum_batch_proofs_device then pm_accum_decide_device: the reference's verify_proof for B
+        proofs.  d_status receives the accumulator's words and then the decider's (a proof with a
+        non-zero word is rejected without a pairing); returns the device pointers (ok, quads, status)."""
+        self.accum_batch_proofs_device(shape, B, vk_repr, d_proofs, stride, d_inst, d_challenges, d_quads, d_h,
+                                       d_status)
+        self.accum_decide_device(pairing, B, d_quads, d_ok, d_status_in=d_status, d_status=d_status, d_gt=d_gt)
+        return d_ok, d_quads, d_status
 
     def fft(self, curve, values, omega, scale=None):
         """pm_fft: natural-order NTT of values ((2^k, 4) u64 Montgomery) with

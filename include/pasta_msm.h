@@ -926,6 +926,69 @@ int pm_accum_batch_proofs_device(pm_ctx* ctx, int curve, const pm_proof_shape* s
                                  const void* d_instance_points, void* d_challenges, void* d_out_quads,
                                  void* d_out_h_eval, void* d_out_status);
 
+/* ---- BN254 pairing decider -----------------------------
+ * The fork's verify_proof returns (Choice, efw); the accumulator entries above
+ * deliver efw.  These entries deliver the Choice: for an accumulator quad
+ * (w, zw, f, e), where e is already negated (multiopen.rs:490-492),
+ *     ok = [ e(w, s_g2) e(-(zw + f + e), g2) == 1 ]
+ * per item, with ParamsVerifier's s_g2 = [tau]G2 and g2.  BN254 only: the
+ * entries take no curve argument.
+ *
+ * Pairing: optimal ate, loop scalar 6x + 2 (x = 4965661367192848881) from the
+ * top bit down, over Fp2 = Fp[u]/(u^2+1), Fp6 = Fp2[v]/(v^3 - (9+u)),
+ * Fp12 = Fp6[w]/(w^2 - v), the D-type twist y^2 = x^3 + 3/(9+u); the exponent
+ * of the final exponentiation is exactly (p^12 - 1)/r (no cofactor).
+ *
+ * G2 point (assumed layout, the in-memory pairing_bn256 G2Affine): 16 x u64 =
+ *   x.c0[4], x.c1[4], y.c0[4], y.c1[4], each Montgomery with R = 2^256 and
+ *   canonical.
+ * pm_pairing_create checks on the host, once, that both points are on the
+ *   twist and of order r (an off-curve, wrong-order, non-canonical or identity
+ *   point is PM_ERR_ARG), and computes every line coefficient of both Miller
+ *   loops (inversions included): the device never touches G2 arithmetic.  With
+ *   a context the tables are uploaded to its device and the object may be used
+ *   by any context of that device; ctx may be NULL for a host-only object
+ *   (pm_accum_decide_host).  pm_pairing_info: line evaluations per pairing,
+ *   bytes of the device table, lanes per pairing product (any output pointer
+ *   may be NULL).  pm_pairing_release: NULL is fine.
+ * pm_pairing_check_device: d_pairs B x 2 x 8 u64, affine G1 points (A, C) as
+ *   everywhere in this header ((0,0) = identity);
+ *   ok = [e(A, s_g2) e(C, g2) == 1].  An identity point contributes 1 (not an
+ *   error).  A point that is neither (0,0) nor on y^2 = x^3 + 3 gives ok = 0
+ *   and status bit PM_DECIDE_NOT_ON_CURVE.
+ * pm_accum_decide_device: d_quads B x 4 x 8 u64 as the accumulator entries
+ *   write them; A = w, C = -(zw + f + e), the sum by the complete group law on
+ *   the device.  The accumulator's d_out_status can be passed as d_status_in.
+ * d_status_in (may be NULL): B x u32; a non-zero word gives ok = 0 without
+ *   evaluation and is passed through to d_out_status.
+ * d_out_ok: B x u32, 1 = accepted, 0 = rejected.  d_out_status (may be NULL):
+ *   B x u32.  d_out_gt (may be NULL): B x 48 u64, the final-exponentiated
+ *   product as 12 Fp values of 4 x u64, canonical, Montgomery with R = 2^256,
+ *   in the tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ... c1.c2.c1; all zero for
+ *   an item that was not evaluated (status != 0).
+ * pm_accum_decide: the host-pointer form (staged through the context).
+ * pm_accum_decide_host: the same check on the CPU, on the process's threads
+ *   (at most 16; one pool kept for the process, so concurrent calls take
+ *   turns); it needs no device and no context, and gives the same words as the
+ *   device forms.
+ * B == 0 succeeds and writes nothing.  PM_ERR_ARG, checked before the context
+ *   is looked at: a null pm_pairing, input or out_ok; then a null context, a
+ *   pm_pairing created without a context or for another device.
+ *   PM_ERR_UNSUPPORTED: B > 2^24. */
+#define PM_DECIDE_NOT_ON_CURVE 8u
+typedef struct pm_pairing pm_pairing;
+int pm_pairing_create(pm_ctx* ctx, const uint64_t g2[16], const uint64_t s_g2[16], pm_pairing** out);
+int pm_pairing_info(const pm_pairing* pr, uint32_t* steps, size_t* table_bytes, uint32_t* lanes_per_pairing);
+int pm_pairing_release(pm_pairing* pr);
+int pm_pairing_check_device(pm_ctx* ctx, const pm_pairing* pr, size_t B, const void* d_pairs /* B x 2 x 8 */,
+                            const void* d_status_in, void* d_out_ok, void* d_out_status, void* d_out_gt);
+int pm_accum_decide_device(pm_ctx* ctx, const pm_pairing* pr, size_t B, const void* d_quads /* B x 4 x 8 */,
+                           const void* d_status_in, void* d_out_ok, void* d_out_status, void* d_out_gt);
+int pm_accum_decide(pm_ctx* ctx, const pm_pairing* pr, size_t B, const uint64_t* quads, const uint32_t* status_in,
+                    uint32_t* out_ok, uint32_t* out_status, uint64_t* out_gt);
+int pm_accum_decide_host(const pm_pairing* pr, size_t B, const uint64_t* quads, const uint32_t* status_in,
+                         uint32_t* out_ok, uint32_t* out_status, uint64_t* out_gt);
+
 #ifdef __cplusplus
 }
 #endif
