@@ -43,6 +43,7 @@ ACCUM_CURVES = (PALLAS, VESTA, BN254)
 PROOF_BAD_POINT = 8
 PROOF_BAD_SCALAR = 16
 DECIDE_NOT_ON_CURVE = 8  # PM_DECIDE_NOT_ON_CURVE
+DECIDE_LOCATE = 1  # PM_DECIDE_LOCATE
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
@@ -392,6 +393,15 @@ def _load():
         "pm_accum_decide_device": ([_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
         "pm_accum_decide": ([_vp, _vp, ctypes.c_size_t, _u64p, _u32p, _u32p, _u32p, _u64p], ctypes.c_int),
         "pm_accum_decide_host": ([_vp, ctypes.c_size_t, _u64p, _u32p, _u32p, _u32p, _u64p], ctypes.c_int),
+        "pm_accum_decide_batch_device": ([_vp, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_char_p, ctypes.c_uint32, _u32p,
+                                          _vp, _vp, _u64p, ctypes.c_char_p], ctypes.c_int),
+        "pm_accum_decide_batch": ([_vp, _vp, ctypes.c_size_t, _u64p, _u32p, ctypes.c_char_p, ctypes.c_uint32, _u32p,
+                                   _u32p, _u32p, _u64p, ctypes.c_char_p], ctypes.c_int),
+        "pm_accum_decide_batch_host": ([_vp, ctypes.c_size_t, _u64p, _u32p, ctypes.c_char_p, ctypes.c_uint32, _u32p,
+                                        _u32p, _u32p, _u64p, ctypes.c_char_p], ctypes.c_int),
+        "pm_verify_proofs_batch_device": ([_vp, ctypes.c_int, ctypes.POINTER(PmProofShape), ctypes.c_size_t, _u64p,
+                                           _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_char_p,
+                                           ctypes.c_uint32, _u32p, _vp, _u64p, ctypes.c_char_p], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if not hasattr(L, name) and os.environ.get("PM_LIB"):
@@ -758,6 +768,33 @@ def accum_decide_host(pairing: Pairing, quads, status_in=None, want_gt=False):
     return (ok, st, gt) if want_gt else (ok, st)
 
 
+def _seed_arg(seed):
+    """32 bytes or None -> (argument, buffer that receives the seed used)"""
+    if seed is not None:
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the batch decider's seed is 32 bytes")
+    return seed, ctypes.create_string_buffer(32)
+
+
+def accum_decide_batch_host(pairing: Pairing, quads, status_in=None, seed=None, locate=False):
+    """pm_accum_decide_batch_host: one pairing check for the whole batch,
+    ok = [e(sum r_i w_i, s_g2) e(sum r_i C_i, g2) == 1], on the CPU (no device, no context).
+    seed: 32 bytes fixed after the proofs and unknown to their makers, or None (drawn from the OS).
+    -> dict(ok, status (B,), pair (2, 8) = L then R, seed[, item_ok (B,) with locate])."""
+    q, B, si, _, st, _ = _decide_args(quads, status_in, False)
+    sd, used = _seed_arg(seed)
+    ok = np.zeros(1, dtype=np.uint32)
+    pair = np.zeros((2, 8), dtype=np.uint64)
+    item = np.zeros(B, dtype=np.uint32) if locate else None
+    _check(lib().pm_accum_decide_batch_host(pairing.h, B, _p(q), _u32(si), sd, DECIDE_LOCATE if locate else 0,
+                                            _u32(ok), _u32(item), _u32(st), _p(pair), used))
+    r = dict(ok=int(ok[0]), status=st, pair=pair, seed=used.raw)
+    if locate:
+        r["item_ok"] = item
+    return r
+
+
 def quotient_eval_host(shape: ProofShape, scalars, x, challenges):
     """pm_quotient_eval_host: the compiled program on the CPU at R points.
     scalars (R, scalars_per_proof, 4), x (R, 4), challenges (R, 16) [theta,
@@ -1122,6 +1159,48 @@ class Context:
         _check(lib().pm_accum_decide(self.h, pairing.h, B, _p(q), _u32(si), _u32(ok), _u32(st),
                                      _p(gt) if want_gt else None))
         return (ok, st, gt) if want_gt else (ok, st)
+
+    def accum_decide_batch_device(self, pairing: Pairing, B, d_quads, d_status_in=0, d_status=0, seed=None,
+                                  d_item_ok=0, locate=False):
+        """pm_accum_decide_batch_device: one pairing check for B accumulator quads (device pointers).
+        -> dict(ok, pair (2, 8) = L then R, seed); with locate d_item_ok receives the per-proof words."""
+        sd, used = _seed_arg(seed)
+        ok = np.zeros(1, dtype=np.uint32)
+        pair = np.zeros((2, 8), dtype=np.uint64)
+        _check(lib().pm_accum_decide_batch_device(self.h, pairing.h, B, _vp(d_quads), _vp(d_status_in or None), sd,
+                                                  DECIDE_LOCATE if locate else 0, _u32(ok), _vp(d_item_ok or None),
+                                                  _vp(d_status or None), _p(pair), used))
+        return dict(ok=int(ok[0]), pair=pair, seed=used.raw)
+
+    def accum_decide_batch(self, pairing: Pairing, quads, status_in=None, seed=None, locate=False):
+        """pm_accum_decide_batch: host arrays in and out, as accum_decide_batch_host."""
+        q, B, si, _, st, _ = _decide_args(quads, status_in, False)
+        sd, used = _seed_arg(seed)
+        ok = np.zeros(1, dtype=np.uint32)
+        pair = np.zeros((2, 8), dtype=np.uint64)
+        item = np.zeros(B, dtype=np.uint32) if locate else None
+        _check(lib().pm_accum_decide_batch(self.h, pairing.h, B, _p(q), _u32(si), sd, DECIDE_LOCATE if locate else 0,
+                                           _u32(ok), _u32(item), _u32(st), _p(pair), used))
+        r = dict(ok=int(ok[0]), status=st, pair=pair, seed=used.raw)
+        if locate:
+            r["item_ok"] = item
+        return r
+
+    def verify_proofs_batch_device(self, shape: ProofShape, pairing: Pairing, B, vk_repr, d_proofs, stride, d_inst,
+                                   d_challenges, d_quads, d_status, seed=None, d_item_ok=0, locate=False, d_h=0):
+        """pm_verify_proofs_batch_device: the accumulator from the proof bytes, then the batch decider on
+        the quads where they lie: verify_proof's (Choice, efw) for B proofs in one call.
+        -> dict(ok, pair, seed); d_quads and d_status hold the quads and the status words."""
+        vk = np.ascontiguousarray(vk_repr, dtype=np.uint64).reshape(4)
+        sd, used = _seed_arg(seed)
+        ok = np.zeros(1, dtype=np.uint32)
+        pair = np.zeros((2, 8), dtype=np.uint64)
+        _check(lib().pm_verify_proofs_batch_device(self.h, shape.curve, ctypes.byref(shape.c), B, _p(vk),
+                                                   _vp(d_proofs), stride, _vp(d_inst or None), _vp(d_challenges),
+                                                   _vp(d_quads), _vp(d_h or None), _vp(d_status), pairing.h, sd,
+                                                   DECIDE_LOCATE if locate else 0, _u32(ok), _vp(d_item_ok or None),
+                                                   _p(pair), used))
+        return dict(ok=int(ok[0]), pair=pair, seed=used.raw)
 
     def verify_proofs_device(self, shape: ProofShape, pairing: Pairing, B, vk_repr, d_proofs, stride, d_inst,
                              d_challenges, d_quads, d_status, d_ok, d_h=0, d_gt=0):

@@ -989,6 +989,67 @@ int pm_accum_decide(pm_ctx* ctx, const pm_pairing* pr, size_t B, const uint64_t*
 int pm_accum_decide_host(const pm_pairing* pr, size_t B, const uint64_t* quads, const uint32_t* status_in,
                          uint32_t* out_ok, uint32_t* out_status, uint64_t* out_gt);
 
+/* ---- Batch decider --------------------------------------
+ * "Are all B proofs valid?" with ONE pairing product instead of B: with 128-bit
+ * coefficients r_i,
+ *     L = sum r_i w_i,   R = sum r_i C_i,   C_i = -(zw_i + f_i + e_i),
+ *     ok = [ e(L, s_g2) e(R, g2) == 1 ].
+ * Every accepted batch of the per-proof decider is accepted.  A batch with a
+ * proof the per-proof decider rejects is rejected except with probability
+ * about 2^-127 over the seed.  SOUNDNESS CONDITION: the seed must be fixed after
+ * the proofs are fixed and must be unknown to whoever made them (with a known
+ * seed two invalid proofs can be made to cancel).  BN254 only.
+ *
+ * r_i = the first 16 bytes, little-endian, of BLAKE2b-512 with the
+ *   personalisation "pm-batch-decide" (zero-padded to 16 bytes) over
+ *   seed[32] || le64(i); used as it comes (a zero is not special-cased).
+ * Item status: a non-zero d_status_in word is passed through; a point that is
+ *   neither (0,0) nor on the curve gives PM_DECIDE_NOT_ON_CURVE.  An item with a
+ *   non-zero status makes ok = 0 and contributes nothing to L and R.  An
+ *   identity w_i or C_i contributes nothing and is not an error.  ok = 1 iff
+ *   every status is 0 and the product is 1; L = R = identity gives 1.
+ * seed: 32 bytes, or NULL: the library draws them from the OS (the source of
+ *   the drop-in cache key; its failure is PM_ERR_HIP).  out_seed (32 bytes,
+ *   may be NULL) receives the seed that was used, so a result can be reproduced.
+ * out_ok: one u32 in host memory.  out_pair (may be NULL): 2 x 8 u64 in host
+ *   memory, L then R, affine as everywhere in this header.
+ * d_out_status (may be NULL): B x u32, may be d_status_in itself.
+ * flags: PM_DECIDE_LOCATE with d_out_item_ok (B x u32) non-NULL: an accepted
+ *   batch writes all ones; a rejected batch runs pm_accum_decide_device on the
+ *   same quads and d_out_item_ok receives its words.  Without the flag
+ *   d_out_item_ok is not touched.  Any other flag bit is PM_ERR_ARG.
+ * pm_accum_decide_batch: the host-pointer form (staged through the context).
+ * pm_accum_decide_batch_host: the same definition on the CPU (one thread), no
+ *   context: the parity form and the CPU baseline; the same words as the device
+ *   forms.
+ * pm_verify_proofs_batch_device: pm_accum_batch_proofs_device (same arguments,
+ *   curve must be PM_CURVE_BN254) and then the batch decider on d_out_quads and
+ *   d_out_status where they lie on the device: the fork's
+ *   verify_proof(...) -> (Choice, efw) for a batch, in one call.  d_out_status
+ *   is required here: it carries the decoder's and the replay's status words to
+ *   the decider and receives the decider's.
+ * B == 0 succeeds and writes ok = 1 (and zero out_pair).  PM_ERR_ARG, checked
+ *   before the context is looked at: a null pm_pairing, input or out_ok, an
+ *   unknown flag bit; then a null context, a pm_pairing created without a
+ *   context or for another device.  PM_ERR_UNSUPPORTED: B > 2^24. */
+#define PM_DECIDE_LOCATE 1u
+int pm_accum_decide_batch_device(pm_ctx* ctx, const pm_pairing* pr, size_t B, const void* d_quads /* B x 4 x 8 */,
+                                 const void* d_status_in, const uint8_t* seed /* 32 bytes or NULL */, uint32_t flags,
+                                 uint32_t* out_ok, void* d_out_item_ok, void* d_out_status,
+                                 uint64_t* out_pair /* 2 x 8 */, uint8_t* out_seed /* 32 bytes */);
+int pm_accum_decide_batch(pm_ctx* ctx, const pm_pairing* pr, size_t B, const uint64_t* quads,
+                          const uint32_t* status_in, const uint8_t* seed, uint32_t flags, uint32_t* out_ok,
+                          uint32_t* out_item_ok, uint32_t* out_status, uint64_t* out_pair, uint8_t* out_seed);
+int pm_accum_decide_batch_host(const pm_pairing* pr, size_t B, const uint64_t* quads, const uint32_t* status_in,
+                               const uint8_t* seed, uint32_t flags, uint32_t* out_ok, uint32_t* out_item_ok,
+                               uint32_t* out_status, uint64_t* out_pair, uint8_t* out_seed);
+int pm_verify_proofs_batch_device(pm_ctx* ctx, int curve, const pm_proof_shape* shape, size_t B,
+                                  const uint64_t vk_repr[4], const void* d_proofs, size_t stride,
+                                  const void* d_instance_points, void* d_challenges, void* d_out_quads,
+                                  void* d_out_h_eval, void* d_out_status, const pm_pairing* pr, const uint8_t* seed,
+                                  uint32_t flags, uint32_t* out_ok, void* d_out_item_ok, uint64_t* out_pair,
+                                  uint8_t* out_seed);
+
 #ifdef __cplusplus
 }
 #endif
