@@ -1,5 +1,6 @@
-// The host plans of the MSM and accumulator drivers (msm_plan.hpp,
-// accum_plan.hpp) as text, for tests/test_plan_native.py: g++ -O2 -std=c++17,
+// The host plans of the MSM and accumulator drivers and of the pairing decider
+// (msm_plan.hpp, accum_plan.hpp, pairing_plan.hpp) as text, for
+// tests/test_plan_native.py and tests/pairing_lazy_model.py: g++ -O2 -std=c++17,
 // no HIP.  One query per line on stdin, one line of key=value fields per
 // query on stdout (lists as comma-separated values):
 //   consts
@@ -17,6 +18,8 @@
 //                                           acc_path
 //   terms nfixed nperm qdeg p_h p_W nsets { len { kind idx eval } * len } * nsets
 //                                           acc_terms of the rotation sets given as (ref kind, ref index, eval)
+//   pairing                                 pairing_plan.hpp: the program's words (prog), step_doubles of every
+//                                           step (doubles), kFrob as 2 x 6 x 2 x 4 words (frob) and the geometry
 // An unknown query prints "error=..." and the program exits with status 2.
 #include <cstdio>
 #include <iostream>
@@ -26,6 +29,7 @@
 
 #include "../../halo2-aggregation_amd/csrc/accum_plan.hpp"
 #include "../../halo2-aggregation_amd/csrc/msm_plan.hpp"
+#include "../../halo2-aggregation_amd/csrc/pairing_plan.hpp"
 
 using namespace pm;
 
@@ -103,6 +107,22 @@ static void dump_schedule(const MsmSchedule& s) {
   }
 }
 
+static void pairing_query() {
+  namespace pp = pm::pairing;
+  kv("kSteps", pp::kSteps), kv("kProgOps", pp::kProgOps), kv("n", pp::kProgram.n), kv("kSlots", pp::kSlots);
+  kv("kPairG", pp::kPairG), kv("kPairPerBlock", pp::kPairPerBlock), kv("kLdsWords", pp::kLdsWords);
+  kv("kOpMul", pp::kOpMul), kv("kOpLine", pp::kOpLine), kv("kOpFrob", pp::kOpFrob), kv("kOpConj", pp::kOpConj);
+  kv("kOpScaleInv", pp::kOpScaleInv);
+  list("prog", std::vector<uint32_t>(pp::kProgram.w, pp::kProgram.w + pp::kProgOps));
+  std::vector<uint32_t> dbl;
+  for (int s = 0; s < pp::kSteps; s++) dbl.push_back(pp::step_doubles(s) ? 1u : 0u);
+  list("doubles", dbl);
+  std::printf("frob=");
+  const uint64_t* f = &pp::kFrob[0][0][0][0];
+  for (int i = 0; i < 2 * 6 * 2 * 4; i++) std::printf(i ? ",%llu" : "%llu", (unsigned long long)f[i]);
+  std::printf(" ");
+}
+
 static bool terms_query(std::istringstream& in) {
   uint32_t nfixed, nperm, qdeg, p_h, p_W, nsets;
   if (!(in >> nfixed >> nperm >> qdeg >> p_h >> p_W >> nsets)) return false;
@@ -146,6 +166,8 @@ int main() {
       const size_t na = a.size();
       if (cmd == "consts" && na == 0) {
         consts();
+      } else if (cmd == "pairing" && na == 0) {
+        pairing_query();
       } else if (cmd == "msm" && na == 3) {
         dump_plan(make_plan((size_t)a[0], (int)a[1], (int)a[2]));
       } else if (cmd == "parts" && na == 4) {

@@ -74,6 +74,42 @@ def batch(B, tau=TAU):
             np.array([p[3] for p in pick], dtype=np.uint32), np.array([p[4] for p in pick], dtype=np.uint32))
 
 
+WALK_REJECT_EVERY = 3    # items i = 2 mod 3 carry the next item's e
+WALK_STATUS_EVERY = 97   # items i = 96 mod 97 carry a non-zero status_in
+WALK_OFF_CURVE = 4       # this item's zw is not on the curve
+
+
+def walk(B, tau=TAU, a0=70001, b0=8101, c0=9203):
+    """B distinct items from walks, no scalar multiplication per item:
+    a_i = a0 + i, b_i = b0 + i, c_i = c0 + i, d_i = a_i tau - b_i - c_i, so w, zw and f advance
+    by G and e by [tau - 2]G, one affine addition each.  Item i is accepted unless
+      i = 2 mod 3: it carries d_(i+1) in place of d_i (off by tau - 2 != 0),
+      i = 96 mod 97: status_in is non-zero (passed through, nothing evaluated),
+      i = WALK_OFF_CURVE: the y of zw has a bit flipped (PM_DECIDE_NOT_ON_CURVE = 8).
+    -> (quads (B, 4, 8), status_in (B,), ok (B,), status (B,)), stated from this construction."""
+    assert (tau - 2) % C.r and B < WALK_STATUS_EVERY * 255
+    step_e = pt(tau - 2)
+    w, zw, f, e = pt(a0), pt(b0), pt(c0), pt(solve_d(a0, b0, c0, tau))
+    q = np.zeros((B, 4, 8), dtype=np.uint64)
+    si = np.zeros(B, dtype=np.uint32)
+    ok = np.ones(B, dtype=np.uint32)
+    for i in range(B):
+        e_next = C.add(e, step_e)
+        reject = i % WALK_REJECT_EVERY == WALK_REJECT_EVERY - 1
+        q[i] = [words(w), words(zw), words(f), words(e_next if reject else e)]
+        if reject:
+            ok[i] = 0
+        if i % WALK_STATUS_EVERY == WALK_STATUS_EVERY - 1:
+            si[i], ok[i] = 0x10 + i // WALK_STATUS_EVERY, 0
+        w, zw, f, e = C.add(w, C.gen), C.add(zw, C.gen), C.add(f, C.gen), e_next
+    st = si.copy()
+    if B > WALK_OFF_CURVE:
+        assert ok[WALK_OFF_CURVE] == 1   # it would have been accepted
+        q[WALK_OFF_CURVE, 1, 4] ^= np.uint64(2)
+        ok[WALK_OFF_CURVE], st[WALK_OFF_CURVE] = 0, 8
+    return q, si, ok, st
+
+
 def g2_words(Q):
     return np.array(PR.g2_words(Q), dtype=np.uint64)
 

@@ -1,7 +1,7 @@
 """tests/native/plan_dump.cpp from Python: the host plans of the MSM and
-accumulator drivers (csrc/msm_plan.hpp, csrc/accum_plan.hpp) asked of the
-compiled code instead of read from its text.  build() compiles the program
-once per process with g++ (no HIP, no GPU); ask() sends queries and returns
+accumulator drivers and of the pairing decider (csrc/msm_plan.hpp,
+csrc/accum_plan.hpp, csrc/pairing_plan.hpp) asked of the compiled code
+instead of read from its text.  build() compiles the program once per process with g++ (no HIP, no GPU); ask() sends queries and returns
 one dict of fields per query."""
 import os
 import subprocess
@@ -19,7 +19,7 @@ def build(tmp_path_factory):
     return _EXE["exe"]
 
 
-LISTS = ("pstart", "termsrc", "qprog", "pairs")   # always lists, whatever their length
+LISTS = ("pstart", "termsrc", "qprog", "pairs", "prog", "doubles", "frob")   # always lists, whatever their length
 
 
 def _field(k, v):

@@ -93,3 +93,16 @@ def test_plan_constants_match_pow():
             got = tuple(sum(next(it) << (64 * i) for i in range(4)) for _ in range(2))
             assert got == want, (j, k)
     assert PR.f2_pow(PR.XI, 2 * (PR.P - 1) // 6) == PR.FROB_X and PR.f2_pow(PR.XI, 3 * (PR.P - 1) // 6) == PR.FROB_Y
+
+
+def test_walk_items_decide_as_constructed(pairing):
+    """pairing_util.walk: distinct items, and the host form decides them as the construction states"""
+    q, si, ok, st = U.walk(200)
+    assert len({q[i].tobytes() for i in range(200)}) == 200
+    assert list(np.flatnonzero(si)) == [96, 193] and list(np.flatnonzero(st)) == [U.WALK_OFF_CURVE, 96, 193]
+    assert st[U.WALK_OFF_CURVE] == H.DECIDE_NOT_ON_CURVE
+    assert [int(v) for v in ok[:9]] == [1, 1, 0, 1, 0, 0, 1, 1, 0] and ok[96] == 0 and ok.sum() == 131
+    h_ok, h_st, h_gt = H.accum_decide_host(pairing, q, si, want_gt=True)
+    assert np.array_equal(h_ok, ok) and np.array_equal(h_st, st)
+    for i in (0, 2, 199):
+        assert np.array_equal(h_gt[i], U.ref_gt_words(q[i])), i
