@@ -834,6 +834,8 @@ int vk_repr_impl(const uint8_t digest[64], uint64_t out[4]) {
 #include "domain_engine.hpp"
 #include "quotient_engine.hpp"
 #include "lookup_engine.hpp"
+#include "ecfft_engine.hpp"
+#include "ecfft_host.hpp"
 
 // One place per engine entry: make_curve_ops fills the table by member name.
 // Its explicit instantiation is visible to both compilation passes, so the
@@ -888,12 +890,28 @@ CurveOps with_lookup_ops(CurveOps o) {
   o.lookup_permute = &lookup_permute_impl<Cv>;
   return o;
 }
+// ... and the point transform's behind those, likewise.
+template <class Cv>
+int fft_points_host_impl(uint64_t* points, uint32_t logn, const uint64_t omega[4], const uint64_t* scale,
+                         int threads) {
+  if (!ecfft::fft_points_host<Cv>(points, logn, omega, scale, threads))
+    return set_error(PM_ERR_ARG, "omega is not a primitive 2^log_n-th root of unity");
+  return PM_OK;
+}
+template <class Cv>
+CurveOps with_ecfft_ops(CurveOps o) {
+  o.fft_points = &ecfft_device_impl<Cv>;
+  o.fft_points_host = &fft_points_host_impl<Cv>;
+  o.fft_points_omega_ok = &ecfft::omega_has_order<typename Cv::Scalar>;
+  return o;
+}
 }  // namespace pm
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PM_OPS_TABLE(Cv, name)
 #else
-#define PM_OPS_TABLE(Cv, name) const CurveOps name = with_lookup_ops<Cv>(make_curve_ops<Cv>());
+#define PM_OPS_TABLE(Cv, name) \
+  const CurveOps name = with_ecfft_ops<Cv>(with_lookup_ops<Cv>(make_curve_ops<Cv>()));
 #endif
 #define PM_DEFINE_CURVE_OPS(Cv, name)            \
   namespace pm {                                 \
@@ -902,5 +920,6 @@ CurveOps with_lookup_ops(CurveOps o) {
   template int transcript_device_impl<Cv>(Ctx*, const pm_proof_shape*, size_t, const uint64_t*, const void*, \
                                           const void*, void*, void*); \
   template CurveOps with_lookup_ops<Cv>(CurveOps); \
+  template CurveOps with_ecfft_ops<Cv>(CurveOps); \
   PM_OPS_TABLE(Cv, name)                         \
   }

@@ -250,6 +250,10 @@ struct DomJob {
   size_t C, keep;
   uint32_t flags;
 };
+// best_fft over curve points (ecfft_engine.hpp): the longest transform is the largest base set an MSM
+// takes; cached code tables per context (48 B per twiddle, n/2 twiddles: 192 MiB at 2^23)
+constexpr uint32_t kEcfftMaxLog = 26;
+constexpr size_t kEcfftTwiddleSlots = 2;
 struct NttTwiddles {
   int curve = -1;
   uint32_t logn = 0;
@@ -351,6 +355,8 @@ struct pm_ctx {
   uint64_t acc_vkpow_gen = ~0ull;  // acc_vkpow.gen when the tables were built
   std::vector<pm::NttTwiddles> ntt_tw;  // cached twiddle segments (pm_fft*)
   uint64_t ntt_clock = 0;
+  std::vector<pm::NttTwiddles> ecfft_tw;  // cached twiddle code tables (pm_fft_points*)
+  uint64_t ecfft_clock = 0;
   void* h_pinned = nullptr;  // MSM host terms: two slots (batch pipelining)
   void* h_pinned_dev = nullptr;  // its device address (hipHostGetDevicePointer, once per allocation)
   size_t h_pinned_cap = 0;
@@ -468,6 +474,13 @@ struct CurveOps {
   int (*lookup_compress)(Ctx* ctx, const void* const* d_cols, size_t m, size_t n, const uint64_t* theta, void* d_out);
   int (*lookup_permute)(Ctx* ctx, const void* const* d_a, const void* const* d_s, size_t P, size_t usable,
                         void* const* d_out_a, void* const* d_out_s, uint32_t* out_status);
+  // best_fft over curve points (ecfft_engine.hpp): n = 2^logn affine points in place; the host form
+  // (ecfft_host.hpp) returns PM_ERR_ARG when omega has not order n
+  int (*fft_points)(Ctx* ctx, int curve, void* d_points, uint32_t logn, const uint64_t omega[4],
+                    const uint64_t* scale);
+  int (*fft_points_host)(uint64_t* points, uint32_t logn, const uint64_t omega[4], const uint64_t* scale,
+                         int threads);
+  bool (*fft_points_omega_ok)(const uint64_t omega[4], uint32_t logn);
 };
 extern const CurveOps kPallasOps, kVestaOps, kBn254Ops;
 

@@ -402,6 +402,9 @@ def _load():
         "pm_verify_proofs_batch_device": ([_vp, ctypes.c_int, ctypes.POINTER(PmProofShape), ctypes.c_size_t, _u64p,
                                            _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_char_p,
                                            ctypes.c_uint32, _u32p, _vp, _u64p, ctypes.c_char_p], ctypes.c_int),
+        "pm_fft_points_device": ([_vp, ctypes.c_int, _vp, ctypes.c_uint32, _u64p, _u64p], ctypes.c_int),
+        "pm_fft_points": ([_vp, ctypes.c_int, _u64p, ctypes.c_uint32, _u64p, _u64p], ctypes.c_int),
+        "pm_fft_points_host": ([ctypes.c_int, _u64p, ctypes.c_uint32, _u64p, _u64p, ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if not hasattr(L, name) and os.environ.get("PM_LIB"):
@@ -444,6 +447,26 @@ def _p(a):
 
 def _as_u64(a, cols):
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, cols)
+
+
+def _fft_points_args(points, omega, scale):
+    a = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8).copy()
+    n = a.shape[0]
+    k = n.bit_length() - 1
+    if n == 0 or n != 1 << k:
+        raise ValueError("length must be a power of two")
+    w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
+    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.uint64).reshape(4)
+    return a, k, w, sc
+
+
+def fft_points_host(curve, points, omega, scale=None, threads=1):
+    """pm_fft_points_host: best_fft over curve points on the CPU (no context):
+    out[k] = [scale] sum_j [omega^(jk)] points[j]; points (2^k, 8) u64 affine
+    Montgomery, omega / scale (4,) u64 Montgomery; returns a new array."""
+    a, k, w, sc = _fft_points_args(points, omega, scale)
+    _check(lib().pm_fft_points_host(curve, _p(a), k, _p(w), None if sc is None else _p(sc), threads))
+    return a
 
 
 def best_multiexp(curve, coeffs, bases, canonical=False):
@@ -1229,6 +1252,20 @@ class Context:
         w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
         sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.uint64).reshape(4)
         _check(lib().pm_fft_device(self.h, curve, _vp(d_data), log_n, _p(w), None if sc is None else _p(sc)))
+
+    def fft_points(self, curve, points, omega, scale=None):
+        """pm_fft_points: best_fft over curve points (the SRS's Lagrange basis
+        is fft_points(g, omega^-1, n^-1)); points (2^k, 8) u64 affine
+        Montgomery; returns a new array."""
+        a, k, w, sc = _fft_points_args(points, omega, scale)
+        _check(lib().pm_fft_points(self.h, curve, _p(a), k, _p(w), None if sc is None else _p(sc)))
+        return a
+
+    def fft_points_device(self, curve, d_points, log_n, omega, scale=None):
+        """pm_fft_points_device: 2^log_n points at d_points, in place."""
+        w = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.uint64).reshape(4)
+        _check(lib().pm_fft_points_device(self.h, curve, _vp(d_points), log_n, _p(w), None if sc is None else _p(sc)))
 
     # ---- polynomial openings (pm_poly_eval* / pm_multiopen_*): d_polys is a
     # sequence of device pointers, each to n Montgomery scalars

@@ -1050,6 +1050,39 @@ int pm_verify_proofs_batch_device(pm_ctx* ctx, int curve, const pm_proof_shape* 
                                   uint32_t flags, uint32_t* out_ok, void* d_out_item_ok, uint64_t* out_pair,
                                   uint8_t* out_seed);
 
+/* ---- NTT over the group: the SRS's Lagrange basis -------
+ * halo2's best_fft is generic over Group; pm_fft* is its scalar half, this is
+ * the half over curve points:
+ *
+ *     out[k] = [scale] sum_j [omega^{jk}] in[j],    0 <= k < n = 2^log_n
+ *
+ * in place, natural order in and out.  Points are the boundary's affine form
+ * (8 x u64, Montgomery R = 2^256, (0,0) the identity); the results are affine
+ * and canonical, an identity result is (0,0), so they are unique: the three
+ * entries agree limb for limb.  Inputs are assumed to be on the curve, as for
+ * pm_msm; they are not checked.  omega (4 x u64 Montgomery, canonical) must be a
+ * primitive 2^log_n-th root of unity in the curve's scalar field; scale
+ * (likewise, or NULL: no scaling pass) may be any scalar, scale = 0 gives n
+ * identities.  log_n = 0 is legal: out[0] = [scale] in[0].
+ *   g_lagrange = pm_fft_points(g, omega^-1, scale = n^-1)
+ * as ParamsKZG::setup computes it from the monomial basis g.
+ *
+ * pm_fft_points_device: n points in device memory, on the context's stream.
+ * pm_fft_points: the host-pointer form, staged through the context.
+ * pm_fft_points_host: the same definition on the CPU, no context: the parity
+ *   form and the CPU baseline, on `threads` host threads (0 or 1: the caller's).
+ * PM_ERR_ARG, checked before the context is looked at: a null pointer or omega,
+ *   an unknown curve, omega not of exact order n (omega^(n/2) != -1; at n = 1,
+ *   omega != 1); then a null context.  PM_ERR_UNSUPPORTED: log_n > 26.
+ * Context scratch is grow-only: 48 B per twiddle, n/2 twiddles, cached per
+ *   (curve, log_n, omega) in two slots; the host-pointer form stages 64 n B. */
+int pm_fft_points_device(pm_ctx* ctx, int curve, void* d_points, uint32_t log_n, const uint64_t omega[4],
+                         const uint64_t* scale /* may be NULL */);
+int pm_fft_points(pm_ctx* ctx, int curve, uint64_t* points, uint32_t log_n, const uint64_t omega[4],
+                  const uint64_t* scale);
+int pm_fft_points_host(int curve, uint64_t* points, uint32_t log_n, const uint64_t omega[4], const uint64_t* scale,
+                       int threads);
+
 #ifdef __cplusplus
 }
 #endif
